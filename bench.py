@@ -18,15 +18,22 @@ the rows dealt cyclically over the ranks, one RCCL all-gather + one local SpMM p
 (sslrec_amd/shard.py; --shard-mode all_gather | pipelined | reduce_scatter makes one of these the headline instead).
 Each carries local SpMM time, the step's collectives timed alone, and the overlap fraction.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line; its roofline comes from the timed region itself:
   roofline     : HBM roofline of the dominant kernel (the SpMM), from HIP-event timings of
                  every 5th SpMM launch inside the timed region (rotating through the launches of a step; see run_eager)
                  and the algorithmic bytes of SURVEY.md §8(d) (entries*8 + (rows+1)*4 + X read once + Y written once
-                 [+ 2 passes for the fused accumulator]);
+                 [+ 2 passes for the fused accumulator]).
+With --full the line also carries what takes runs of its own:
+  roofline     : + the in-run PMC traffic, the gather ceiling, the step with the zero-row hint and as one hipGraph;
   cpu_baseline : the reference's CPU expression (torch.spmm over the uncoalesced COO,
                  lightgcn.py:28-29) timed on this box's cores on the SAME graph (oracle port);
   extras       : masked-propagation rate, fused InfoNCE pairs/s with its FP32-MFMA roofline
-                 fraction, and full training-step times (N=1 only).
+                 fraction, and full training-step times (N=1 only);
+  + roofline_infonce, multi_gpu_predicted, rccl_check, the cfg1 / cfg3 / cfg4 lines (N=1), and at N > 1 the second
+  decomposition with the collectives timed alone (multi_gpu, decompositions).
+
+--dump-outputs DIR writes what the last timed step computed (loss, BPR loss, gradients of the embedding tables) as
+DIR/<name>.npy in float32: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -44,6 +51,7 @@ sys.path.insert(0, ROOT)
 MFMA_BF16_PEAK_TF = 2500.0        # dense bf16 MFMA peak (MI355X_MICROARCH.md; AMD's 5 PF headline includes 2:1 sparsity)
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is achievable
 MFMA_F32_PEAK_TF = 157.3     # v_mfma_f32_32x32x2_f32 dense peak
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: larger outputs are written as a fixed, seeded sample of their rows
 
 
 def build_graph_host(name):
@@ -92,6 +100,21 @@ def cpu_baseline(rows, cols, vals, n, d, budget_s=15.0):
     return {'value': vals.size / med, 'unit': 'edges/s', 'cores': thr, 'kind': 'port',
             'sample': '%d x torch.spmm(uncoalesced COO %dx%d nnz=%d, X[%d,%d]) forward, median %.1f ms with %d threads (best of 16 / 64 / all %d cores)'
                       % (reps, n, n, vals.size, n, d, med * 1e3, thr, os.cpu_count())}
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs: name -> tensor as out_dir/<name>.npy in float32.  Past DUMP_LIMIT_BYTES in all, every array of two or more
+    dimensions keeps the same seeded sample of its rows, and out_dir/<name>_rows.npy (float64) says which rows those are."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim >= 2:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES * 0.75 / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + '_rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def time_events(fn, reps, warmup=2):
@@ -508,7 +531,7 @@ def rccl_check_child(args):
     import subprocess
     if os.environ.get('SSLREC_BENCH_CHILD') == '1':
         return {'skipped': 'child run'}
-    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '6', '--warmup', '2', '--no-cpu-baseline', '--no-extras',
+    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '6', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-extras',
            '--no-configs', '--no-live-traffic', '--workload', args.workload, '--dim', str(args.dim), '--layers', str(args.layers)]
     env = dict(os.environ, SSLREC_BENCH_CHILD='1', SSLREC_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
@@ -553,7 +576,7 @@ def measure_traffic_live(args):
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             out_dir = os.path.join(tmp, counter)
             cmd = [prof, '--pmc', counter, '--kernel-trace', '--output-format', 'csv', '-d', out_dir, '-o', 'p', '--', sys.executable,
-                   os.path.abspath(__file__), '--steps', '6', '--warmup', '2', '--no-cpu-baseline', '--no-extras', '--no-configs', '--no-live-traffic',
+                   os.path.abspath(__file__), '--steps', '6', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-extras', '--no-configs', '--no-live-traffic',
                    '--workload', args.workload, '--dim', str(args.dim), '--layers', str(args.layers)]
             env = dict(os.environ, SSLREC_BENCH_CHILD='1', SSLREC_SPARSE_GRAD='0', TMPDIR='/tmp')
             subprocess.run(cmd, cwd='/tmp', env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=180, check=True)
@@ -674,6 +697,11 @@ def main():
     ap.add_argument('--no-configs', action='store_true', help='default run: skip the cfg1 / cfg3 / cfg4 lines')
     ap.add_argument('--eager-step', action='store_true',
                     help='feature mode: issue the step as ~40 eager launches instead of two captured hipGraphs around the all-gather')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline (see the module docstring); the --no-* switches '
+                         'leave parts of it out.  Without it the run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)')
     args = ap.parse_args()
 
     if args.config != 'cfg2':
@@ -682,6 +710,8 @@ def main():
         from bench_configs import run_config
         print(json.dumps(run_config(args.config, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline)))
         return
+    if not args.full:         # a plain run: nothing that takes runs of its own beside the timed steps
+        args.no_cpu_baseline = args.no_extras = args.no_configs = args.no_live_traffic = args.no_second_decomposition = True
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         spawn_ranks(args)                 # does not return
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL prints "Librccl path : ..." through C stdio, which
@@ -782,8 +812,13 @@ def main():
                                                'HIP events around every %dth SpMM launch of the timed region (%d of its %d launches; the sampled launch '
                                                'rotates through the %d of a step)' % (every, len(recs), len(prof), len(prof) // max(1, args.steps)))
 
+    def keep_outputs(tensors):      # --dump-outputs: the headline's last timed step, written before anything else runs
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, tensors)
+
     graph = None
     results = {}               # decomposition -> dict(elapsed, recs, timing, step kind)
+    last = {}                  # the loss parts of the latest step (detached: no autograd node outlives its step)
     if not dist_path:
         from sslrec_amd.graph import PropGraph
         graph = PropGraph(rows, cols, vals, (n, n), dev)
@@ -795,47 +830,51 @@ def main():
             s, reg = ops.propagate_sum(graph, e0, L, reg_weight=reg_weight)      # (the regularizer's gradient rides on the last backward product)
             loss, _bpr = ops.bpr_loss_stacked(s, trn.shape[0], *batch, divisor=B, add=reg)      # bpr + reg (lightgcn.py:54) from the BPR kernel's finishing step
             loss.backward(one)
+            last['loss'], last['bpr_loss'] = loss.detach(), _bpr.detach()
         # The headline counts 2 L nnz propagated edges per step, so every one of them is really multiplied: the library's default of
         # telling the first backward product which rows of the BPR gradient are zero (ops.SPARSE_GRAD, same result, that launch 80 -> 55 us)
         # is switched OFF for the timed region and reported separately below.
         sparse_default, ops.SPARSE_GRAD = ops.SPARSE_GRAD, False
         elapsed, recs, timing = run_eager(step)
+        keep_outputs({'loss': last['loss'], 'bpr_loss': last['bpr_loss'],
+                      'user_embeds_grad': e0.grad[:trn.shape[0]], 'item_embeds_grad': e0.grad[trn.shape[0]:]})
         results['single'] = dict(elapsed=elapsed, recs=recs, timing=timing, graphed=False, n_launches=run_eager.n_launches,
                                  by_position=run_eager.by_position)
         headline = 'single'
         ops.SPARSE_GRAD = sparse_default
-        hint_elapsed, hint_recs = 0.0, []
-        if sparse_default:      # (SSLREC_SPARSE_GRAD=0, e.g. the profiling passes of tools/gpu_profile.sh: dense launches only)
-            hint_elapsed, hint_recs, _ = run_eager(step)
-        hinted = [r for r in hint_recs if r[5] is not None]
-        # the same step replayed as ONE captured hipGraph (no Python, no event records between the launches), without and with the hint
-        graphed = {}
-        try:
-            for label, flag in ((('dense', False), ('zero_row_hint', True)) if sparse_default else (('dense', False),)):
-                ops.SPARSE_GRAD = flag
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(3):
+        if args.full:
+            hint_elapsed, hint_recs = 0.0, []
+            if sparse_default:      # (SSLREC_SPARSE_GRAD=0, e.g. the profiling passes of tools/gpu_profile.sh: dense launches only)
+                hint_elapsed, hint_recs, _ = run_eager(step)
+            hinted = [r for r in hint_recs if r[5] is not None]
+            # the same step replayed as ONE captured hipGraph (no Python, no event records between the launches), without and with the hint
+            graphed = {}
+            try:
+                for label, flag in ((('dense', False), ('zero_row_hint', True)) if sparse_default else (('dense', False),)):
+                    ops.SPARSE_GRAD = flag
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        for _ in range(3):
+                            step()
+                    torch.cuda.current_stream().wait_stream(side)
+                    torch.cuda.synchronize()
+                    cg = torch.cuda.CUDAGraph()
+                    e0.grad = None
+                    with torch.cuda.graph(cg):
                         step()
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.synchronize()
-                cg = torch.cuda.CUDAGraph()
-                e0.grad = None
-                with torch.cuda.graph(cg):
-                    step()
-                graphed['ms_per_step_' + label] = timed_steps(cg.replay, args.steps, args.warmup, barrier) / args.steps * 1e3
-                del cg
-        except Exception as exc:
-            graphed['error'] = repr(exc)[:300]
-        ops.SPARSE_GRAD = sparse_default
-        results['single']['as_one_hip_graph'] = graphed
-        results['single']['zero_row_hint'] = None if not hinted else {
-            'ms_per_step': hint_elapsed / args.steps * 1e3,
-            'hinted_launch_us': float(np.mean([r[4] for r in hinted])) * 1e6 if hinted else None,
-            'hinted_launch_algorithmic_bytes': launches_summary(hinted)[1] if hinted else None,
-            'note': 'the same K steps with the library default ops.SPARSE_GRAD on: the first backward product of a step skips the entries '
-                    'of the rows the BPR loss did not write (<= 3B of N); bit-identical gradients'}
+                    graphed['ms_per_step_' + label] = timed_steps(cg.replay, args.steps, args.warmup, barrier) / args.steps * 1e3
+                    del cg
+            except Exception as exc:
+                graphed['error'] = repr(exc)[:300]
+            ops.SPARSE_GRAD = sparse_default
+            results['single']['as_one_hip_graph'] = graphed
+            results['single']['zero_row_hint'] = None if not hinted else {
+                'ms_per_step': hint_elapsed / args.steps * 1e3,
+                'hinted_launch_us': float(np.mean([r[4] for r in hinted])) * 1e6 if hinted else None,
+                'hinted_launch_algorithmic_bytes': launches_summary(hinted)[1] if hinted else None,
+                'note': 'the same K steps with the library default ops.SPARSE_GRAD on: the first backward product of a step skips the entries '
+                        'of the rows the BPR loss did not write (<= 3B of N); bit-identical gradients'}
     else:
         feature_ok = d % world == 0 and d // world in (8, 16, 32, 64, 128, 256)
         headline = args.shard_mode
@@ -873,11 +912,15 @@ def main():
                     recs = [(m[0], m[1], m[2], m[3], ms * 1e-3, None, m[6] if len(m) > 6 else 0) for m, ms, cnt in stamps.read() for _ in range(1)]
                     n_exec = [cnt for _, _, cnt in stamps.read()]
                     assert all(c == args.steps for c in n_exec), n_exec       # every captured launch ran once per timed step
+                    if mode == headline:
+                        keep_outputs({'bpr_loss': gstep.loss_bpr, 'reg_local': gstep.reg_local, 'embeds_grad_local': model.local_embeds.grad})
                     results[mode] = dict(elapsed=max_over_ranks(elapsed), recs=recs * args.steps, graphed=True,
                                          timing='device wall clock inside every SpMM launch of the timed region (first workgroup start to last '
                                                 'workgroup end, accumulated over the replays; HIP events cannot be recorded inside a captured hipGraph)')
                 else:
                     elapsed, recs, timing = run_eager(eager_step)
+                    if mode == headline:
+                        keep_outputs(dict(model.last_parts, embeds_grad_local=model.local_embeds.grad))
                     results[mode] = dict(elapsed=elapsed, recs=recs, timing=timing, graphed=False, n_launches=run_eager.n_launches)
                 del model
             else:
@@ -889,6 +932,8 @@ def main():
                     model.local_embeds.grad = None
                     model.lightgcn_loss(batch, reg_weight).backward()
                 elapsed, recs, timing = run_eager(step)
+                if mode == headline:
+                    keep_outputs(dict(model.last_parts, embeds_grad_local=model.local_embeds.grad))
                 results[mode] = dict(elapsed=elapsed, recs=recs, timing=timing, graphed=False, n_launches=run_eager.n_launches)
                 del model, sg
             torch.cuda.empty_cache()
@@ -903,7 +948,7 @@ def main():
     achieved = avg_bytes / avg_s / 1e9
     traffic = traffic_src = None
     tf = os.path.join(ROOT, 'profiles', 'spmm_traffic.json')
-    live_note = None
+    live_note = None if args.full else 'measured by --full runs'
     if not dist_path and rank == 0 and not args.no_extras:      # (the quick experiment lines of the tools skip it with --no-extras)
         traffic, traffic_src = measure_traffic_live(args)
         if traffic is None:
@@ -957,7 +1002,7 @@ def main():
     # multi-GPU: per decomposition the local SpMM time, the step's collectives timed alone, the overlap (SURVEY.md §8e asks
     # for edges/s with and without the per-layer collective)
     multi = None
-    if dist_path:
+    if dist_path and args.full:
         from sslrec_amd.shard import all_gather_rows, all_reduce_sum, reduce_scatter_rows, rows_per_rank, shards_pipelined
         n_per = rows_per_rank(n, world)
         xs = torch.randn(n_per, d, device=dev)

@@ -2445,7 +2445,7 @@ def test_bench_runs_its_multi_gpu_path_over_rccl_with_one_rank():
     env = dict(os.environ, SSLREC_BENCH_FORCE_DIST='1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR'):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'yelp'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'yelp', '--full'],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(out.stdout.strip().splitlines()) == 1, out.stdout[-2000:]      # the contract: ONE line on stdout, whatever RCCL prints
@@ -2637,7 +2637,7 @@ def test_bench_starts_its_own_ranks_without_a_launcher(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SSLREC_BENCH_ONE_DEVICE='1')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None)
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--workload', 'tiny'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--workload', 'tiny', '--full'],
                          env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]

@@ -41,7 +41,7 @@ if main and 'FETCH_SIZE' in summary[main]:
     traffic = {
         'kernel': main,
         'measured_in_round': round_tag, 'measured_at_commit': commit,
-        'command': 'rocprofv3 --pmc <C> --kernel-trace -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras '
+        'command': 'rocprofv3 --pmc <C> --kernel-trace -- python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras '
                    '(separate passes for FETCH_SIZE, WRITE_SIZE, TCC_HIT_sum+TCC_MISS_sum; tools/gpu_profile.sh)',
         'FETCH_SIZE_KB_raw': s['FETCH_SIZE']['mean'], 'WRITE_SIZE_KB_raw': s.get('WRITE_SIZE', {}).get('mean'),
         'correction': 'FETCH_SIZE doubled (gfx950 counts 128-B fabric requests at 64 B); WRITE_SIZE used as reported (uncalibrated)',

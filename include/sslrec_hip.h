@@ -618,6 +618,50 @@ size_t sslrec_scatter_ws_bytes(int32_t B);
 int sslrec_scatter_add_rows_f32(const float *src, const int64_t *idx, int32_t B, int32_t d,
                                 float *dst, void *ws, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Learned edge weights (csrc/sddmm.hip): AdaptiveMask, models/aug_utils.py:73-79, as DCCF calls it behind four index_selects
+ * that materialize [nnz, d] tensors, models/general_cf/dccf.py:83-90.  Here an ENTRY is one COO entry of the adjacency in the
+ * caller's order (the numbering of EdgeDrop masks); every per-entry array is fp32 [nnz] in that order.  The pattern is a plan's
+ * plain CSR on the device, int32: rowptr [n_rows + 1], col [nnz], perm [nnz] (CSR position -> entry id) and row_of_entry [nnz]
+ * (CSR position -> row).  The transposed plan numbers the entries alike, so per-column sums are row sums over ITS CSR: no scatter,
+ * no atomics, every sum in a fixed order.  Embedding sizes: 8, 16, 32, 64, 128, 256.
+ * ---------------------------------------------------------------------------------- */
+
+/* Sampled dense-dense product: out[perm[k]] = <A[row_of_entry[k], :], B[col[k], :]> * ra[row] * cb[col] for every CSR position k
+ * (the gathers plus t.sum(head * tail, dim=1) of aug_utils.py:75 and dccf.py:83-84, one row gather per entry and side instead of
+ * two [nnz, d] tensors).  A [n_rows, d], B [n_cols, d] row-major, may alias; ra [n_rows] / cb [n_cols] nullable (= 1): with the
+ * inverse row norms the result is the cosine, without a normalized copy of the table (F.normalize, aug_utils.py:73-74).  Work is
+ * split by entries, so a hub row does not serialize a wave. */
+int sslrec_sddmm_f32(const int32_t *row_of_entry, const int32_t *col, const int32_t *perm, int32_t n_rows, int32_t n_cols, int32_t nnz,
+                     const float *A, const float *B, int32_t d, const float *ra, const float *cb, float *out, void *stream);
+
+/* Rows of more than SSLREC_EDGE_LONG_ROW entries get a workgroup of their own in the two row normalizations below: long_rows
+ * [n_long] must then list exactly those rows (n_long = 0: every row is walked by one 16-lane group, whatever its length). */
+#define SSLREC_EDGE_LONG_ROW 512
+
+/* aug_utils.py:75-79: alpha = (c + 1) / 2, s_h = sum of alpha over row h, inv_s[h] = 1 / s_h (0 where that is not finite:
+ * .pow(-1).nan_to_num(0, 0, 0)), w[e] = alpha[e] * inv_s[row(e)].  c, w [nnz] in entry order; inv_s [n_rows]. */
+int sslrec_edge_rownorm_fwd_f32(const int32_t *rowptr, const int32_t *perm, int32_t n_rows, const int32_t *long_rows, int32_t n_long,
+                                const float *c, float *w, float *inv_s, void *stream);
+
+/* its backward (autograd of aug_utils.py:75-79): dc[e] = inv_s[h] / 2 * (dw[e] - sum over row h of w * dw), and the two per-node
+ * sums the cosine's backward needs, p_head[h] = sum of dc * c over row h and p_tail[t] = sum of dc * c over the entries INTO t --
+ * the latter over the transposed plan's CSR (rowptr_t [n_cols + 1], perm_t, long_rows_t).  dc [nnz]; p_head [n_rows]; p_tail [n_cols]. */
+int sslrec_edge_rownorm_bwd_f32(const int32_t *rowptr, const int32_t *perm, int32_t n_rows, const int32_t *long_rows, int32_t n_long,
+                                const int32_t *rowptr_t, const int32_t *perm_t, int32_t n_cols, const int32_t *long_rows_t,
+                                int32_t n_long_t, const float *dw, const float *w, const float *inv_s, const float *c, float *dc,
+                                float *p_head, float *p_tail, void *stream);
+
+/* n[r] = 1 / max(||S[r, :]||_2, 1e-12), the factor of F.normalize (aug_utils.py:73-74); normalized (nullable) [n_rows, d] = n (.) S,
+ * which the valued SpMMs of the backward multiply. */
+int sslrec_row_invnorm_f32(const float *S, int32_t n_rows, int32_t d, float *n, float *normalized, void *stream);
+
+/* Finish of the cosine's backward: with G[r, :] = sum over the entries of node r of dc * (normalized other end) -- one valued SpMM
+ * per side -- dS[r, :] = n[r] * (G[r, :] - (p_a[r] + p_b[r]) * n[r] * S[r, :]); rows whose norm is below 1e-12 were divided by the
+ * constant and get n[r] * G[r, :].  p_b nullable (two-table form: one side per table); dS may be G. */
+int sslrec_cosine_finish_f32(const float *S, const float *n, const float *G, const float *p_a, const float *p_b, int32_t n_rows,
+                             int32_t d, float *dS, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

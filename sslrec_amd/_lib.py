@@ -164,6 +164,11 @@ SIGNATURES = {
     'sslrec_weighted_sum4_f32': (C.c_int, [_P, _F, _P, _F, _P, _F, _P, _F, _P, _P]),
     'sslrec_scalar_scale2_f32': (C.c_int, [_P, _F, _F, _P, _P]),
     'sslrec_add_tables_f32': (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    'sslrec_sddmm_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    'sslrec_edge_rownorm_fwd_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    'sslrec_edge_rownorm_bwd_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_row_invnorm_f32': (C.c_int, [_P, _I, _I, _P, _P, _P]),
+    'sslrec_cosine_finish_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
 }
 
 _lib = None

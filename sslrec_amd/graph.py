@@ -27,6 +27,7 @@ FLAG_NO_XCD_SPLIT = 1
 # row, sslrec_amd/feature_shard.py); beyond the swept layout's size limits they run on the row-bundled streamed layout
 SWEPT_DIMS = (8, 16, 32, 64, 128, 256)
 BUNDLED_DIMS = (8, 16)
+EDGE_LONG_ROW = 512    # SSLREC_EDGE_LONG_ROW of include/sslrec_hip.h
 
 
 def swept_enabled():
@@ -361,6 +362,28 @@ class CsrPlan:
                     lay = SweptLayout(self, d)
             self._swept[d] = lay
         return self._swept[d]
+
+    def host_csr(self):
+        """the plain CSR as int32 host arrays for the per-entry kernels (csrc/sddmm.hip): rowptr [n_rows + 1], col [nnz], perm [nnz]
+        (CSR position -> the CALLER's entry id: perm_host is taken before a column re-labelling rebuilds the native plan, so it
+        already is the native perm composed with perm_outer), row_of_entry [nnz] (CSR position -> row) and long_rows
+        (rows of more than EDGE_LONG_ROW entries, which the row normalizations give a workgroup each); cached"""
+        if getattr(self, '_host_csr', None) is None:
+            deg = np.diff(self.rowptr_host)
+            self._host_csr = {
+                'rowptr': np.ascontiguousarray(self.rowptr_host, dtype=np.int32),
+                'col': np.ascontiguousarray(self.csr_col_host, dtype=np.int32),
+                'perm': np.ascontiguousarray(self.perm_host, dtype=np.int32),
+                'row_of_entry': np.repeat(np.arange(self.n_rows, dtype=np.int32), deg),
+                'long_rows': np.flatnonzero(deg > EDGE_LONG_ROW).astype(np.int32),
+            }
+        return self._host_csr
+
+    def device_csr(self):
+        """host_csr() on the device (int32 tensors, uploaded on first use, cached)"""
+        if getattr(self, '_device_csr', None) is None:
+            self._device_csr = {k: torch.from_numpy(v).to(self.device) for k, v in self.host_csr().items()}
+        return self._device_csr
 
     def swept_edge_map(self, d):
         """element of the swept layout -> original COO entry (-1 for pads), on the device"""

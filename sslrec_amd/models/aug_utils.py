@@ -1,6 +1,8 @@
 """Augmentation modules feeding the hot path; same class names and call signatures as the
 reference's models/aug_utils.py (EdgeDrop :11-31, EmbedPerturb :118-132, SvdDecomposition
-:82-98).  The random draws are taken from the global torch CPU generator in exactly the
+:82-98, AdaptiveMask :52-80).  AdaptiveMask is the one exception to "same call signature": it takes the NODE table and folds in
+the gathers its only caller does first (dccf.py:83-86), so no [nnz, d] tensor is ever built; the reference's two-tensor call raises
+a TypeError that says so.  The random draws are taken from the global torch CPU generator in exactly the
 reference's order and shapes (parity mode), unless `device_rng` is given (perf mode: a
 `sslrec_amd.rng.PhiloxState`; the kernels COMPUTE mask bits / noise rows in place, nothing is drawn, stored or
 copied -- statistically equivalent, not bit-equal).  With `sslrec_amd.rng.enable_host_replay` (the Trainer's default on a
@@ -10,7 +12,7 @@ import torch as t
 import torch.nn.functional as F
 from torch import nn
 
-from ..graph import DroppedView, graph_of
+from ..graph import DroppedView, PropGraph, graph_of
 
 
 class _PinnedDraws:
@@ -104,6 +106,45 @@ class EmbedPerturb(nn.Module):
             u = u.materialize()
         noise = (F.normalize(u, p=2) * t.sign(embeds)) * self.eps
         return embeds + noise
+
+
+class AdaptiveMask(nn.Module):
+    """Adaptively mask edges with a learned weight (reference :52-80, used in DCCF): G_values[e] = alpha[e] / (sum of alpha over
+    the head node's entries), alpha = (cos(embeds[head[e]], embeds[tail[e]]) + 1) / 2.  `head_list`, `tail_list`, `matrix_shape` are
+    the reference's constructor arguments; one `PropGraph` with unit values is built from the lists (`.graph`), and every per-entry
+    result is in the entry order of the lists.
+
+    forward(embeds) takes the node table [N, d] -- the four index_selects of dccf.py:83-86 are folded into the kernels -- and returns
+    (G_indices, G_values) like the reference, G_values differentiable in `embeds`.  For a rectangular pattern pass the two node
+    tables: forward(head_table, tail_table=...).  propagate(G_values, x) is the product dccf.py:89-90 forms with them."""
+
+    def __init__(self, head_list, tail_list, matrix_shape, device=None):
+        super().__init__()
+        self.head_list, self.tail_list, self.matrix_shape = head_list, tail_list, tuple(int(v) for v in matrix_shape)
+        heads, tails = t.as_tensor(head_list).long(), t.as_tensor(tail_list).long()
+        if heads.dim() != 1 or heads.shape != tails.shape:
+            raise ValueError('head_list and tail_list: two lists of one length expected')
+        if device is None:
+            device = heads.device if heads.is_cuda else ('cuda' if t.cuda.is_available() else 'cpu')
+        device = t.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = t.device('cuda', t.cuda.current_device())
+        self.G_indices = t.stack([heads, tails], dim=0).to(device)
+        import numpy as np
+        self.graph = PropGraph(heads.cpu().numpy(), tails.cpu().numpy(), np.ones(heads.numel(), dtype=np.float32), self.matrix_shape, device)
+
+    def forward(self, embeds, tail_embeds=None, tail_table=None):
+        from .. import ops
+        if tail_embeds is not None:
+            raise TypeError('AdaptiveMask takes the NODE table: forward(embeds [N, d]) gathers both ends of every edge itself (the '
+                            'index_selects of dccf.py:83-86 are fused in); for a rectangular pattern call forward(head_table, '
+                            'tail_table=tail_table).  Per-entry [nnz, d] tensors are not accepted.')
+        return self.G_indices, ops.edge_cosine_weights(self.graph, embeds, tail_table)
+
+    def propagate(self, G_values, x):
+        """A(G_values) x, differentiable in both (torch_sparse.spmm of dccf.py:89-90)"""
+        from .. import ops
+        return ops.spmm_valued(self.graph, G_values, x)
 
 
 class SvdDecomposition(nn.Module):

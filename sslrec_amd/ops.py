@@ -421,6 +421,190 @@ def spmm(adj, x):
 
 
 # ----------------------------------------------------------------------------------------------
+# learned edge weights (AdaptiveMask, reference aug_utils.py:52-80 as dccf.py:82-90 calls it): SDDMM, the row normalization
+# of entry values, and a SpMM that is differentiable in its VALUES.  Per-entry arrays are fp32 [nnz] in the caller's entry
+# order (the numbering of EdgeDrop masks and RevaluedView.vals); nothing of size nnz x d is ever stored.  (csrc/sddmm.hip)
+# ----------------------------------------------------------------------------------------------
+EDGE_DIMS = (8, 16, 32, 64, 128, 256)
+
+
+def _pattern_graph(adj, what, device=None):
+    """the PropGraph whose sparsity pattern `adj` carries; an edge-dropped view is refused (its pattern is not the graph's)"""
+    adj = _as_adj(adj)
+    if isinstance(adj, DroppedView):
+        raise ValueError('%s: an edge-dropped view is not supported (an edge-dropped adaptive graph is out of scope)' % what)
+    graph = adj.graph if isinstance(adj, RevaluedView) else adj
+    gd = graph.device
+    if device is not None and (gd.type != device.type or (gd.index is not None and device.index is not None and gd.index != device.index)):
+        raise ValueError('%s: the graph lives on %s, the tensors on %s' % (what, graph.device, device))
+    return graph
+
+
+def _plan_of(graph, which, what):
+    plan = getattr(graph, which) if which in ('fwd', 'bwd') else None
+    if plan is None:
+        raise ValueError('%s: the graph has no %r plan' % (what, which))
+    return plan
+
+
+def _entry_vec(t, nnz, what):
+    t = _f32c(t)
+    if t.dim() != 1 or t.numel() != nnz:
+        raise ValueError('%s: fp32 [%d] in entry order expected, got %s' % (what, nnz, tuple(t.shape)))
+    return t
+
+
+def sddmm(adj, a, b, which='fwd', row_factor=None, col_factor=None):
+    """out[e] = <a[row(e)], b[col(e)]> * row_factor[row(e)] * col_factor[col(e)] for every entry e of the pattern of `adj` (a PropGraph or
+    a RevaluedView of one; which='bwd': of its transpose, so a has n_cols rows), fp32 [nnz] in the caller's entry order.  a and b may be
+    the same table.  Not differentiable on its own: spmm_valued and edge_cosine_weights carry the gradients."""
+    _need_gpu(a, b, row_factor, col_factor)
+    graph = _pattern_graph(adj, 'sddmm', a.device)
+    plan = _plan_of(graph, which, 'sddmm')
+    a, b = _f32c(a.detach()), _f32c(b.detach())
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != plan.n_rows or b.shape[0] != plan.n_cols or a.shape[1] != b.shape[1]:
+        raise ValueError('sddmm: operands of shapes %s and %s for a %d x %d pattern' % (tuple(a.shape), tuple(b.shape), plan.n_rows, plan.n_cols))
+    d = a.shape[1]
+    if d not in EDGE_DIMS:
+        raise ValueError('embedding size %d not supported by the HIP SDDMM (supported: %s)' % (d, EDGE_DIMS))
+    ra = None if row_factor is None else _f32c(row_factor.detach())
+    cb = None if col_factor is None else _f32c(col_factor.detach())
+    if (ra is not None and ra.numel() != plan.n_rows) or (cb is not None and cb.numel() != plan.n_cols):
+        raise ValueError('sddmm: row_factor [%d] and col_factor [%d] expected' % (plan.n_rows, plan.n_cols))
+    csr = plan.device_csr()
+    out = torch.empty(plan.nnz, dtype=torch.float32, device=a.device)
+    rc = _lib.load().sslrec_sddmm_f32(csr['row_of_entry'].data_ptr(), csr['col'].data_ptr(), csr['perm'].data_ptr(), plan.n_rows, plan.n_cols,
+                                      plan.nnz, a.data_ptr(), b.data_ptr(), d, _ptr(ra), _ptr(cb), out.data_ptr(), _stream())
+    _lib.check(rc, 'sslrec_sddmm_f32')
+    return out
+
+
+def row_invnorm(x, normalized=False):
+    """n [N] = 1 / max(||x[r]||, 1e-12) (F.normalize's factor); normalized=True: (n, n (.) x)"""
+    _need_gpu(x)
+    x = _f32c(x.detach())
+    n = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    xn = torch.empty_like(x) if normalized else None
+    _lib.check(_lib.load().sslrec_row_invnorm_f32(x.data_ptr(), x.shape[0], x.shape[1], n.data_ptr(), _ptr(xn), _stream()),
+               'sslrec_row_invnorm_f32')
+    return (n, xn) if normalized else n
+
+
+def _long(csr):
+    lr = csr['long_rows']
+    return (lr.data_ptr() if lr.numel() else None), lr.numel()
+
+
+def _cosine_finish(s, n, g, p_a, p_b):
+    """dS = n (.) (g - (p_a + p_b) (.) n (.) s), written over g"""
+    _lib.check(_lib.load().sslrec_cosine_finish_f32(s.data_ptr(), n.data_ptr(), g.data_ptr(), p_a.data_ptr(), _ptr(p_b), s.shape[0], s.shape[1],
+                                                    g.data_ptr(), _stream()), 'sslrec_cosine_finish_f32')
+    return g
+
+
+class _EdgeCosineFn(torch.autograd.Function):
+    """w = rownorm((cos(head[row], tail[col]) + 1) / 2); saves c, w, inv_s and the inverse norms -- [nnz] and [N] vectors only"""
+
+    @staticmethod
+    def forward(ctx, head, tail, graph):
+        square = tail is None
+        h = _f32c(head)
+        t = h if square else _f32c(tail)
+        n_h = row_invnorm(h)
+        n_t = n_h if square else row_invnorm(t)
+        c = sddmm(graph, h, t, 'fwd', n_h, n_t)
+        fwd = graph.fwd
+        csr = fwd.device_csr()
+        w = torch.empty_like(c)
+        inv_s = torch.empty(fwd.n_rows, dtype=torch.float32, device=c.device)
+        lr, n_long = _long(csr)
+        _lib.check(_lib.load().sslrec_edge_rownorm_fwd_f32(csr['rowptr'].data_ptr(), csr['perm'].data_ptr(), fwd.n_rows, lr, n_long,
+                                                           c.data_ptr(), w.data_ptr(), inv_s.data_ptr(), _stream()),
+                   'sslrec_edge_rownorm_fwd_f32')
+        ctx.graph, ctx.square = graph, square
+        ctx.save_for_backward(h, t, c, w, inv_s, n_h, n_t)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        h, t, c, w, inv_s, n_h, n_t = ctx.saved_tensors
+        graph, square = ctx.graph, ctx.square
+        fwd, bwd = graph.fwd, graph.bwd
+        dw = _entry_vec(dw, fwd.nnz, 'edge_cosine_weights backward')
+        cf, cb = fwd.device_csr(), bwd.device_csr()
+        dc = torch.empty_like(c)
+        p_head = torch.empty(fwd.n_rows, dtype=torch.float32, device=c.device)
+        p_tail = torch.empty(fwd.n_cols, dtype=torch.float32, device=c.device)
+        lr, n_long = _long(cf)
+        lr_t, n_long_t = _long(cb)
+        rc = _lib.load().sslrec_edge_rownorm_bwd_f32(cf['rowptr'].data_ptr(), cf['perm'].data_ptr(), fwd.n_rows, lr, n_long,
+                                                     cb['rowptr'].data_ptr(), cb['perm'].data_ptr(), fwd.n_cols, lr_t, n_long_t,
+                                                     dw.data_ptr(), w.data_ptr(), inv_s.data_ptr(), c.data_ptr(), dc.data_ptr(),
+                                                     p_head.data_ptr(), p_tail.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_edge_rownorm_bwd_f32')
+        view = RevaluedView(graph, dc)                           # the two valued SpMMs run on the tuned kernels
+        if square:                                               # both ends from one table: the two parts add into one dS
+            _, s_hat = row_invnorm(h, normalized=True)
+            g = spmm_raw(view, s_hat, 'fwd')
+            spmm_raw(view, s_hat, 'bwd', acc_in=g, acc_out=g, want_y=False)
+            return _cosine_finish(h, n_h, g, p_head, p_tail), None, None
+        _, h_hat = row_invnorm(h, normalized=True)
+        _, t_hat = row_invnorm(t, normalized=True)
+        d_h = _cosine_finish(h, n_h, spmm_raw(view, t_hat, 'fwd'), p_head, None)
+        d_t = _cosine_finish(t, n_t, spmm_raw(view, h_hat, 'bwd'), p_tail, None)
+        return d_h, d_t, None
+
+
+def edge_cosine_weights(adj, head_table, tail_table=None):
+    """AdaptiveMask's values (aug_utils.py:73-79) from NODE tables: w[e] = alpha[e] / sum of alpha over the row of e, alpha =
+    (cos(head_table[row(e)], tail_table[col(e)]) + 1) / 2, an empty row's inverse sum being 0.  tail_table=None: both ends from one table
+    (the square adjacency of DCCF).  Differentiable in the tables; fp32 [nnz] in the caller's entry order."""
+    _need_gpu(head_table, tail_table)
+    graph = _pattern_graph(adj, 'edge_cosine_weights', head_table.device)
+    if graph.bwd is None:
+        raise ValueError('edge_cosine_weights: the graph needs its transposed plan')
+    n_rows, n_cols = graph.shape
+    tail_rows = n_rows if tail_table is None else tail_table.shape[0]
+    if head_table.dim() != 2 or head_table.shape[0] != n_rows or tail_rows != n_cols or \
+            (tail_table is not None and tuple(tail_table.shape[1:]) != tuple(head_table.shape[1:])):
+        raise ValueError('edge_cosine_weights: tables of %s / %s rows for a %d x %d pattern' % (head_table.shape[0], tail_rows, n_rows, n_cols))
+    d = head_table.shape[1]
+    dp = _padded_dim(d, EDGE_DIMS)                               # zero columns change neither norms nor dot products
+    return _EdgeCosineFn.apply(_pad_cols(head_table, dp), None if tail_table is None else _pad_cols(tail_table, dp), graph)
+
+
+class _SpmmValuedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vals, x, graph):
+        vals, x = _entry_vec(vals, graph.nnz, 'spmm_valued'), _f32c(x)
+        ctx.graph = graph
+        ctx.save_for_backward(vals, x)
+        return spmm_raw(RevaluedView(graph, vals), x, 'fwd')
+
+    @staticmethod
+    def backward(ctx, gy):
+        vals, x = ctx.saved_tensors
+        gy = _f32c(gy)
+        dx = spmm_raw(RevaluedView(ctx.graph, vals), gy, 'bwd') if ctx.needs_input_grad[1] else None
+        dvals = sddmm(ctx.graph, gy, x, 'fwd') if ctx.needs_input_grad[0] else None
+        return dvals, dx, None
+
+
+def spmm_valued(adj, vals, x):
+    """Y = A(vals) X for the PATTERN of `adj` with the entry values `vals` (fp32 [nnz], caller's entry order; torch_sparse.spmm with
+    learned values, dccf.py:89-90).  Differentiable in both: dX = A(vals)^T dY on the tuned SpMM, dvals[e] = <dY[row(e)], X[col(e)]> by
+    SDDMM.  Embedding sizes without a kernel are zero-padded like ops.spmm."""
+    _need_gpu(vals, x)
+    graph = _pattern_graph(adj, 'spmm_valued', x.device)
+    if graph.bwd is None:
+        raise ValueError('spmm_valued: the graph needs its transposed plan')
+    d = x.shape[1]
+    dp = _spmm_dim(graph, d)
+    y = _SpmmValuedFn.apply(vals, _pad_cols(x, dp), graph)
+    return y if dp == d else y[:, :d]
+
+
+# ----------------------------------------------------------------------------------------------
 # fused L-layer propagation + layer SUM (+ optional per-layer perturbation)
 #   S = E0 + sum_l E_l,  E_l = P_l(A E_{l-1})      (lightgcn.py:31-43 / simgcl.py:20-30)
 # backward:  g_L = G,  g_{l-1} = G + A^T g_l,  dE0 = g_0   (perturbation has unit Jacobian a.e.)

@@ -662,6 +662,31 @@ int sslrec_row_invnorm_f32(const float *S, int32_t n_rows, int32_t d, float *n, 
 int sslrec_cosine_finish_f32(const float *S, const float *n, const float *G, const float *p_a, const float *p_b, int32_t n_rows,
                              int32_t d, float *dS, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Intent-aware aggregation of DCCF (csrc/intent.hip), models/general_cf/dccf.py:77-80:
+ *     u_embeds, i_embeds = torch.split(all_embeds[i], [user_num, item_num], 0)
+ *     u_int_embeds = torch.softmax(u_embeds @ user_intent, dim=1) @ user_intent.T
+ *     i_int_embeds = torch.softmax(i_embeds @ item_intent, dim=1) @ item_intent.T
+ *     int_layer_embeds = torch.concat([u_int_embeds, i_int_embeds], dim=0)
+ * on the stacked table X [N, d] (fp32, row-major): rows [0, n_split) use C_u, rows [n_split, N) use C_i, both [d, K] row-major as the
+ * parameters are stored.  d in {32, 64, 128}, 1 <= K <= 256, 0 <= n_split <= N; the matrix of an EMPTY range may be null.  Nothing
+ * of size N x K is written to global memory: the prototype matrix stays in LDS, the products are exact-fp32 MFMAs, the softmax
+ * subtracts the row maximum.  Every entry point returns SSLREC_E_BADARG before any launch for a null required pointer or a size
+ * outside these ranges; N == 0 returns 0 without a launch. */
+
+/* bytes of the backward's workspace (per-workgroup partial sums of dC); 0 for arguments out of range */
+size_t sslrec_intent_ws_bytes(int32_t N, int32_t n_split, int32_t d, int32_t K);
+
+/* Y [N, d] = softmax(X C) C^T; lse [N] (nullable) receives the log-sum-exp of every row's logits, which the backward needs */
+int sslrec_intent_fwd_f32(const float *X, int32_t N, int32_t n_split, int32_t d, const float *C_u, const float *C_i, int32_t K, float *Y,
+                          float *lse, void *stream);
+
+/* From dY [N, d]: p = exp(X C - lse) recomputed, dp = dY C, dz = p (dp - <p, dp>), dX = dz C^T, dC = sum over the range's rows of
+ * X_r^T dz + dY_r^T p.  dC_u / dC_i [d, K]: required for a non-empty range, zero-filled if given for an empty one.  No atomics:
+ * per-workgroup sums in ws (sslrec_intent_ws_bytes), added in a fixed order by a second launch -- two runs give the same bits. */
+int sslrec_intent_bwd_f32(const float *X, const float *dY, const float *lse, int32_t N, int32_t n_split, int32_t d, const float *C_u,
+                          const float *C_i, int32_t K, float *dX, float *dC_u, float *dC_i, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

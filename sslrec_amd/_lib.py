@@ -169,6 +169,9 @@ SIGNATURES = {
     'sslrec_edge_rownorm_bwd_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     'sslrec_row_invnorm_f32': (C.c_int, [_P, _I, _I, _P, _P, _P]),
     'sslrec_cosine_finish_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    'sslrec_intent_ws_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+    'sslrec_intent_fwd_f32': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    'sslrec_intent_bwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

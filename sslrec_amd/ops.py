@@ -605,6 +605,93 @@ def spmm_valued(adj, vals, x):
 
 
 # ----------------------------------------------------------------------------------------------
+# intent-aware aggregation (dccf.py:77-80): Y = softmax(X C) C^T per row range of the stacked table, nothing of size N x K
+# stored forward or backward (csrc/intent.hip)
+# ----------------------------------------------------------------------------------------------
+INTENT_DIMS = (32, 64, 128)
+INTENT_KMAX = 256
+
+
+class _IntentFn(torch.autograd.Function):
+    """saves X, the matrices and ONE float per row (log-sum-exp of the logits); the backward recomputes the probabilities"""
+
+    @staticmethod
+    def forward(ctx, x, n_split, c_u, c_i):
+        x = _f32c(x)
+        c_u = None if c_u is None else _f32c(c_u)
+        c_i = None if c_i is None else _f32c(c_i)
+        n, d = x.shape
+        k = (c_u if c_u is not None else c_i).shape[1]
+        y = torch.empty_like(x)
+        lse = torch.empty(n, dtype=torch.float32, device=x.device)
+        if n > 0:                                                # (an empty tensor has no address to hand over)
+            rc = _lib.load().sslrec_intent_fwd_f32(x.data_ptr(), n, n_split, d, _ptr(c_u), _ptr(c_i), k, y.data_ptr(), lse.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_intent_fwd_f32')
+        ctx.n_split, ctx.has = n_split, (c_u is not None, c_i is not None)
+        ctx.save_for_backward(x, lse, *[c for c in (c_u, c_i) if c is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, lse, *cs = ctx.saved_tensors
+        cs = list(cs)
+        c_u = cs.pop(0) if ctx.has[0] else None
+        c_i = cs.pop(0) if ctx.has[1] else None
+        gy = _f32c(gy)
+        n, d = x.shape
+        k = (c_u if c_u is not None else c_i).shape[1]
+        lib = _lib.load()
+        dx = torch.empty_like(x)
+        dc_u = None if c_u is None else torch.empty_like(c_u)
+        dc_i = None if c_i is None else torch.empty_like(c_i)
+        if n == 0:
+            return dx, None, (None if dc_u is None else dc_u.zero_()), (None if dc_i is None else dc_i.zero_())
+        ws = torch.empty(lib.sslrec_intent_ws_bytes(n, ctx.n_split, d, k) // 4 + 1, dtype=torch.float32, device=x.device)
+        rc = lib.sslrec_intent_bwd_f32(x.data_ptr(), gy.data_ptr(), lse.data_ptr(), n, ctx.n_split, d, _ptr(c_u), _ptr(c_i), k, dx.data_ptr(),
+                                       _ptr(dc_u), _ptr(dc_i), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_intent_bwd_f32')
+        return dx, None, dc_u, dc_i
+
+
+def _intent_matrix(c, what):
+    if c.dim() != 2 or not 1 <= c.shape[1] <= INTENT_KMAX:
+        raise ValueError('%s: an intent matrix [d, K] with 1 <= K <= %d expected, got %s' % (what, INTENT_KMAX, tuple(c.shape)))
+    return c
+
+
+def intent_aggregate_stacked(table, n_user, user_intent, item_intent):
+    """concat([softmax(U @ user_intent, 1) @ user_intent.T, softmax(I @ item_intent, 1) @ item_intent.T]) for table = [U; I], U its first
+    n_user rows (dccf.py:77-80): both products in ONE launch, no split / concat copies, no [N, K] tensor forward or backward.
+    Differentiable in the table and both matrices ([d, K], K <= 256).  Embedding sizes without a kernel are zero-padded: zero columns
+    of the table and zero rows of the matrices add nothing to any logit, the padded output columns are dropped."""
+    _need_gpu(table, user_intent, item_intent)
+    _intent_matrix(user_intent, 'intent_aggregate_stacked')
+    _intent_matrix(item_intent, 'intent_aggregate_stacked')
+    n_user = int(n_user)
+    if table.dim() != 2 or not 0 <= n_user <= table.shape[0] or user_intent.shape != item_intent.shape or user_intent.shape[0] != table.shape[1]:
+        raise ValueError('intent_aggregate_stacked: table %s, n_user %d, matrices %s / %s' %
+                         (tuple(table.shape), n_user, tuple(user_intent.shape), tuple(item_intent.shape)))
+    d = table.shape[1]
+    dp = _padded_dim(d, INTENT_DIMS)
+    pad_rows = lambda c: c if dp == d else torch.nn.functional.pad(c, (0, 0, 0, dp - d))
+    y = _IntentFn.apply(_pad_cols(table, dp), n_user, pad_rows(user_intent), pad_rows(item_intent))
+    return y if dp == d else y[:, :d]
+
+
+def intent_aggregate(x, intents):
+    """softmax(x @ intents, dim=1) @ intents.T for one table [N, d] and one matrix [d, K]; differentiable in both"""
+    _need_gpu(x, intents)
+    _intent_matrix(intents, 'intent_aggregate')
+    if x.dim() != 2 or intents.shape[0] != x.shape[1]:
+        raise ValueError('intent_aggregate: table %s, matrix %s' % (tuple(x.shape), tuple(intents.shape)))
+    d = x.shape[1]
+    dp = _padded_dim(d, INTENT_DIMS)
+    c = intents if dp == d else torch.nn.functional.pad(intents, (0, 0, 0, dp - d))
+    y = _IntentFn.apply(_pad_cols(x, dp), x.shape[0], c, None)
+    return y if dp == d else y[:, :d]
+
+
+# ----------------------------------------------------------------------------------------------
 # fused L-layer propagation + layer SUM (+ optional per-layer perturbation)
 #   S = E0 + sum_l E_l,  E_l = P_l(A E_{l-1})      (lightgcn.py:31-43 / simgcl.py:20-30)
 # backward:  g_L = G,  g_{l-1} = G + A^T g_l,  dE0 = g_0   (perturbation has unit Jacobian a.e.)

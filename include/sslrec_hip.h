@@ -687,6 +687,36 @@ int sslrec_intent_fwd_f32(const float *X, int32_t N, int32_t n_split, int32_t d,
 int sslrec_intent_bwd_f32(const float *X, const float *dY, const float *lse, int32_t N, int32_t n_split, int32_t d, const float *C_u,
                           const float *C_i, int32_t K, float *dX, float *dC_u, float *dC_i, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * Hypergraph layer of HCCF (csrc/hyper.hip), models/general_cf/hccf.py:43-44, 48-49 and HGNNLayer.forward :105-107:
+ *     uu_hyper = self.user_embeds @ self.user_hyper_embeds * self.mult
+ *     hyper_user_embeds = self.hgnn_layer(F.dropout(uu_hyper, p=1-keep_rate), embeds_list[-1][:self.user_num])
+ *         hids = self.act(adj.T @ embeds);  embeds = self.act(adj @ hids)              (act = LeakyReLU(leaky))
+ * and the same for the items, on the stacked tables E (the parameters) and X (the layer's input), both [N, d] fp32 row-major: rows
+ * [0, n_split) use W_u, rows [n_split, N) use W_i, both [d, K] row-major as the parameters are stored.  d in {32, 64, 128},
+ * 1 <= K <= 256 except d = 128 with K > 128 (two [d, K] matrices exceed LDS: SSLREC_E_BADARG, workspace size 0), 0 <= n_split <= N,
+ * leaky > 0, 0 < keep_rate <= 1; the pointers of an EMPTY range may be null.  Nothing of size N x K is written: A = dropout(E W mult) is
+ * recomputed wherever it is needed, and its mask is computed from the Philox state (see "device-side augmentation RNG"):
+ *     keep(row, k) = floor(u + keep_rate) != 0,  u = uniform number row * 4 ceil(K / 4) + k of call philox_stream
+ * (sslrec_philox_fill_f32 writes the same numbers out); a kept element is scaled by mult / keep_rate.  keep_rate == 1 draws nothing
+ * and philox_state may be null.  No atomics: sums over rows go through per-workgroup slabs in ws, added in a fixed order.
+ * ws: sslrec_hyper_ws_bytes(N, n_split, d, K) bytes of device memory, contents irrelevant on entry, for either call. */
+size_t sslrec_hyper_ws_bytes(int32_t N, int32_t n_split, int32_t d, int32_t K);
+
+/* Y [N, d] = act(A act(A^T X)) per range.  H_u, H_i [d, K] receive act(A^T X) TRANSPOSED (element [j, k] = H[k, j]), which the
+ * backward needs together with Y. */
+int sslrec_hyper_fwd_f32(const float *X, const float *E, int32_t N, int32_t n_split, int32_t d, const float *W_u, const float *W_i, int32_t K,
+                         float mult, float leaky, float keep_rate, const uint64_t *philox_state, uint32_t philox_stream, float *H_u,
+                         float *H_i, float *Y, void *ws, void *stream);
+
+/* From dY [N, d], the forward's Y, H_u, H_i and the SAME philox_state contents and philox_stream: dX, dE [N, d] (separate outputs: where
+ * X and E are one tensor the caller adds them) and dW_u, dW_i [d, K] (zero for an empty range).  The slope of act comes from the sign
+ * of Y and H; at exactly 0 it is `leaky`.  Two runs give the same bits. */
+int sslrec_hyper_bwd_f32(const float *X, const float *E, const float *dY, const float *Y, int32_t N, int32_t n_split, int32_t d,
+                         const float *W_u, const float *W_i, const float *H_u, const float *H_i, int32_t K, float mult, float leaky,
+                         float keep_rate, const uint64_t *philox_state, uint32_t philox_stream, float *dX, float *dE, float *dW_u,
+                         float *dW_i, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,123 +3,17 @@
 // forward and backward in one launch each for both row ranges, without anything of size N x K in global memory: the backward
 // recomputes the probabilities from X, C and one saved float per row (the log-sum-exp of the row's logits).
 //
-// Layout.  A workgroup of 4 waves belongs to ONE row range and keeps that range's C in LDS for its lifetime (row stride
-// 32 KB + 1 floats: rows are read along k by the first product and down i by the second, both free of bank conflicts; the
-// columns K .. 32 KB - 1 are zero).  A wave owns tiles of 32 rows of its range -- tiles are counted per range, so none holds rows
-// of both.  All products are exact-fp32 MFMAs (32x32x2) formed TRANSPOSED, Z^T = C^T X^T: the accumulator then has the tile's ROW
-// on the lane (row = lane & 31) and the logits k = 32 kb + (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) in its registers, so
-//   * the softmax of a row is a sum inside a lane plus ONE exchange with lane ^ 32;
-//   * P^T is already the B operand of the next product Y^T = C P^T (the sum over k may run in any order: a step takes k from the
-//     low half and k + 4 from the high half), no movement between lanes, no LDS.
-// Only dC = X^T dZ + dY^T P sums over rows, i.e. over lanes: dZ^T and P^T go through a 32 x 33 LDS tile per wave, one block of 32
-// logits at a time.  dC has no atomics: a wave keeps its sum in registers over all its tiles, the 4 waves add up in a fixed order in
-// LDS, the workgroup writes its [d, K] slab to the workspace and a second kernel adds the slabs in a fixed order.
+// Layout and the tile helpers: rowtile.h.  The accumulator of the transposed product has the tile's ROW on the lane and the logits in
+// its registers, so the softmax of a row is a sum inside a lane plus ONE exchange with lane ^ 32, and P^T is already the B operand of
+// Y^T = C P^T.  Only dC = X^T dZ + dY^T P sums over rows: dZ^T and P^T go through the wave's transposition tile, and the workgroups'
+// slabs are added in a fixed order by a second kernel -- no atomics.
 #include "common.h"
+#include "rowtile.h"
 
 namespace {
 
-typedef float in_f32x4 __attribute__((ext_vector_type(4)));
-typedef float in_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int IN_WAVES = 4;
 constexpr int IN_FWD_CAP = 1024;       // workgroups per row range at most (each loads C once)
 constexpr int IN_BWD_CAP = 256;        // ... in the backward: one [d, K] slab of the workspace each
-constexpr int IN_TSTRIDE = 33;         // row stride of the per-wave transposition tile
-
-__device__ __forceinline__ void in_wave_sync() {          // LDS traffic between the lanes of ONE wave
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// row blocks of dC a backward workgroup accumulates (16 accumulator registers per 32 x 32 block, at most 128 in all)
-template <int D, int KB> struct InCfg {
-    static constexpr int DB = D / 32;
-    static constexpr int DC = (DB * KB <= 8) ? DB : ((8 / KB) > 0 ? 8 / KB : 1);
-    static constexpr int CHUNKS = DB / DC;
-    static constexpr int KS = KB * 32 + 1;
-    static constexpr int C_FLOATS = D * KS;
-    static constexpr int RED_FLOATS = DC * KB * 16 * 64;
-    static constexpr int BWD_MAIN = C_FLOATS > RED_FLOATS ? C_FLOATS : RED_FLOATS;
-    static constexpr size_t FWD_LDS = (size_t)C_FLOATS * 4;
-    static constexpr size_t BWD_LDS = (size_t)(BWD_MAIN + IN_WAVES * 32 * IN_TSTRIDE) * 4;
-};
-
-struct InRange {
-    const float *C;
-    int lo, hi, g, G;                  // rows [lo, hi), this workgroup's index among the G of the range
-};
-
-__device__ __forceinline__ InRange in_range(const float *C_u, const float *C_i, int N, int n_split, int G_u) {
-    InRange r;
-    if ((int)blockIdx.x < G_u) {
-        r.C = C_u; r.lo = 0; r.hi = n_split; r.g = blockIdx.x; r.G = G_u;
-    } else {
-        r.C = C_i; r.lo = n_split; r.hi = N; r.g = blockIdx.x - G_u; r.G = gridDim.x - G_u;
-    }
-    return r;
-}
-
-template <int D, int KB>
-__device__ __forceinline__ void in_load_c(float *lds, const float *__restrict__ C, int K) {
-    constexpr int KS = KB * 32 + 1;
-    for (int e = threadIdx.x; e < D * KS; e += IN_WAVES * 64) {
-        const int i = e / KS, k = e - i * KS;
-        lds[e] = (k < K) ? C[(size_t)i * K + k] : 0.f;
-    }
-    __syncthreads();
-}
-
-// this lane's half of row `row` of a [*, D] table: columns [half D / 2, (half + 1) D / 2); zeros for a row past the range
-template <int D>
-__device__ __forceinline__ void in_load_half_row(const float *__restrict__ T, long long row, bool valid, int half, float (&v)[D / 2]) {
-    const in_f32x4 *p = reinterpret_cast<const in_f32x4 *>(T + (size_t)row * D + half * (D / 2));
-#pragma unroll
-    for (int j = 0; j < D / 8; ++j) {
-        in_f32x4 q = {0.f, 0.f, 0.f, 0.f};
-        if (valid) q = p[j];
-        v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
-    }
-}
-
-// acc[kb] = (C^T V^T) block kb: acc[kb][reg] = <V_row, C[:, k(kb, reg, half)]>
-template <int D, int KB>
-__device__ __forceinline__ void in_logits(const float *lds, const float (&v)[D / 2], int l32, int half, in_f32x16 (&acc)[KB]) {
-    constexpr int KS = KB * 32 + 1;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[kb][r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < D / 2; ++s)
-            acc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[(half * (D / 2) + s) * KS + kb * 32 + l32], v[s], acc[kb], 0, 0, 0);
-    }
-}
-
-// out[row, :] = sum_k W[row, k] C[:, k] for the accumulator-layout weights W, stored as float4s
-template <int D, int KB>
-__device__ __forceinline__ void in_project_store(const float *lds, const in_f32x16 (&w)[KB], int l32, int half, float *__restrict__ out,
-                                                 long long row, bool valid) {
-    constexpr int KS = KB * 32 + 1;
-#pragma unroll
-    for (int ib = 0; ib < D / 32; ++ib) {
-        in_f32x16 y;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) y[r] = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                y = __builtin_amdgcn_mfma_f32_32x32x2f32(lds[(ib * 32 + l32) * KS + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half], w[kb][r], y, 0,
-                                                         0, 0);
-        if (valid) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                in_f32x4 o = {y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]};
-                *reinterpret_cast<in_f32x4 *>(out + (size_t)row * D + ib * 32 + 8 * q + 4 * half) = o;
-            }
-        }
-    }
-}
 
 template <int D, int KB>
 __global__ __launch_bounds__(256, D * KB <= 128 ? 2 : 1) void intent_fwd_kernel(const float *__restrict__ X, int N, int n_split, const float *__restrict__ C_u,
@@ -248,29 +142,7 @@ __global__ __launch_bounds__(256) void intent_bwd_kernel(const float *__restrict
             }
         }
     }
-    // the 4 waves' sums, added in the order of the waves, then the workgroup's slab
-    float *red = in_lds;
-    for (int w = 0; w < IN_WAVES; ++w) {
-        __syncthreads();                                       // (first round: every wave is done with C)
-        if (wave == w) {
-#pragma unroll
-            for (int a = 0; a < DC; ++a)
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int at = ((a * KB + kb) * 16 + r) * 64 + lane;
-                        red[at] = (w == 0) ? dc[a][kb][r] : red[at] + dc[a][kb][r];
-                    }
-        }
-    }
-    __syncthreads();
-    float *slab = ws + (size_t)blockIdx.x * (D * KP);
-    for (int e = threadIdx.x; e < DC * KB * 16 * 64; e += IN_WAVES * 64) {
-        const int ln = e & 63, r = (e >> 6) & 15, blk = e >> 10, kb = blk % KB, a = blk / KB;
-        const int i = (chunk * DC + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5), k = kb * 32 + (ln & 31);
-        slab[i * KP + k] = red[e];
-    }
+    in_slab_store<D, KB>(in_lds, dc, chunk, ws + (size_t)blockIdx.x * (D * KP));
 }
 
 // dC[i, k] = sum over the range's slabs in index order (four interleaved partial sums, combined in a fixed order)
@@ -295,13 +167,6 @@ __global__ __launch_bounds__(256) void intent_reduce_kernel(const float *__restr
     }
     for (; g < G; ++g) s0 += src[(size_t)g * step];
     out[e] = (s0 + s1) + (s2 + s3);
-}
-
-inline int in_kb(int K) { return K <= 32 ? 1 : (K <= 64 ? 2 : (K <= 128 ? 4 : 8)); }
-
-inline int in_groups(long long rows, int cap) {
-    const long long g = (rows + 32 * IN_WAVES - 1) / (32 * IN_WAVES);
-    return (int)(g < cap ? g : cap);
 }
 
 inline bool in_args_ok(int64_t N, int64_t n_split, int d, int K, const void *C_u, const void *C_i) {

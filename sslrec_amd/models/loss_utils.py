@@ -1,10 +1,10 @@
 """Loss library of the hot path, same names / signatures / return conventions as the
 reference's models/loss_utils.py (cal_bpr_loss :7-10, reg_pick_embeds :13-17, reg_params
-:20-24, cal_infonce_loss :30-39), backed by the fused HIP kernels of sslrec_amd.ops.
+:20-24, cal_infonce_loss :30-39, cal_infonce_loss_spec_nodes :42-51), backed by the fused HIP kernels of sslrec_amd.ops.
 
 `cal_*_gathered` are the table-level forms the in-tree models use: they take the full
 embedding tables plus the batch indices, so the [B, d] gathers of lightgcn.py:49-51 /
-simgcl.py:32-37 are never materialized.  The other eight functions of the upstream file
+simgcl.py:32-37 are never materialized.  The other seven functions of the upstream file
 belong to models outside this path's scope and are not provided.
 """
 from .. import ops
@@ -41,6 +41,25 @@ def cal_infonce_loss_two_sided(stacked1, stacked2, user_num, user_idx, item_idx,
     """cal_infonce_loss(U1[user_idx], U2[user_idx], U2, temp) + cal_infonce_loss(I1[item_idx], I2[item_idx], I2, temp) on the stacked
     [users; items] tables of two views: both terms of simgcl.py:49 / sgl.py:57-59 as one autograd node (no slicing of the tables)"""
     return ops.infonce_loss_two_sided(stacked1, stacked2, user_num, user_idx, item_idx, temp, variant=0, precision=precision)
+
+
+def cal_infonce_loss_spec_nodes(embeds1, embeds2, nodes, temp, precision=None):
+    """-log(nume / deno).mean() over `nodes` with x^ = F.normalize(x + 1e-8), nume = exp(<e1^[n], e2^[n]> / temp) and
+    deno = sum_j exp(<e1^[n], e2^_j> / temp) + 1e-8 (loss_utils.py:42-51), on the fused gathered InfoNCE: no [B, M] tensor.
+
+    The two tables are normalized the reference's way with element-wise torch ops over [N, d]; the kernel normalizes its rows once
+    more, x / sqrt(1e-8 + |x|^2), which moves a unit row by a factor 1 - 5e-9 and a cosine by 1e-8, below fp32 resolution.
+    The 1e-8 added to the denominator is NOT carried: it changes a node's term by log(1 + 1e-8 / deno) <= 1e-8 / deno, and the node's
+    own positive is one of the M summands, so deno >= exp(c / temp) with c its cosine, and deno ~ M for unrelated rows.  For the
+    term to reach the 8 * 2^-23 ~ 1e-6 relative floor the tests hold the loss to (a loss of order log M >= 1), deno would have to
+    fall below 1e-2, i.e. EVERY cosine of the node below temp * ln(1e-2 / M) -- at temp 0.1 and M = 220 below -1, which no cosine
+    is; at temp 1.0 the bound is 1e-8 * e / M.  `precision` (not in the reference): see ops.infonce_loss."""
+    import torch.nn.functional as F
+    from ..ops import _need_gpu
+    _need_gpu(embeds1, embeds2, nodes)
+    normed1 = F.normalize(embeds1 + 1e-8, p=2)
+    normed2 = F.normalize(embeds2 + 1e-8, p=2)
+    return ops.infonce_loss_gathered(normed1, normed2, nodes, temp, variant=0, precision=precision) / nodes.shape[0]
 
 
 def reg_pick_embeds(embeds_list):

@@ -692,6 +692,120 @@ def intent_aggregate(x, intents):
 
 
 # ----------------------------------------------------------------------------------------------
+# hypergraph layer of HCCF (hccf.py:43-44, 48-49, 105-107): A = dropout(E W * mult), H = act(A^T X), Y = act(A H) per row range of the
+# stacked tables, nothing of size N x K stored forward or backward, the dropout mask computed in the kernels (csrc/hyper.hip)
+# ----------------------------------------------------------------------------------------------
+HYPER_DIMS = (32, 64, 128)
+HYPER_KMAX = 256
+
+
+def hyper_fused_ok(d, k):
+    """whether csrc/hyper.hip has kernels for the (padded) embedding size d and K hyperedges: at d = 128 with K > 128 not even two
+    of the [d, K] matrices W, H, dQ fit the 160 KB of LDS, and hyper_propagate_stacked runs the composed torch expression instead"""
+    return not (d == 128 and k > 128)
+
+
+def hyper_keep_mask(state, stream, n_rows, k, keep_rate):
+    """bool [n_rows, k]: the dropout mask the hypergraph kernels compute for call `stream` at the state's current step --
+    floor(u + keep_rate) of EdgeDrop's arithmetic with u = Philox uniform number row * 4 ceil(k / 4) + col of the call (rows of the
+    STACKED table).  For tests and for the composed fallback; the kernels never store it."""
+    from .rng import philox_uniforms
+    n_rows, k = int(n_rows), int(k)
+    kp = (k + 3) // 4 * 4
+    u = philox_uniforms(state, stream, n_rows * kp).view(n_rows, kp)[:, :k]
+    return (u + keep_rate).floor().type(torch.bool)
+
+
+def _hyper_composed(x, e, n_user, w_u, w_i, mult, leaky, keep_rate, mask):
+    """the reference's expression (hccf.py:43-49, 105-107) with the given keep mask"""
+    act = torch.nn.functional.leaky_relu
+
+    def side(xr, er, w, m):
+        a = er @ w * mult
+        if m is not None:
+            a = a * m.to(a.dtype) / keep_rate
+        return act(a @ act(a.T @ xr, leaky), leaky)
+    m_u, m_i = (None, None) if mask is None else (mask[:n_user], mask[n_user:])
+    return torch.concat([side(x[:n_user], e[:n_user], w_u, m_u), side(x[n_user:], e[n_user:], w_i, m_i)], dim=0)
+
+
+class _HyperFn(torch.autograd.Function):
+    """saves X, E, the two matrices, Y and the two H ([d, K] each, kept transposed); the backward recomputes A and the mask"""
+
+    @staticmethod
+    def forward(ctx, x, e, n_split, w_u, w_i, mult, leaky, keep_rate, state, stream):
+        x, e, w_u, w_i = _f32c(x), _f32c(e), _f32c(w_u), _f32c(w_i)
+        n, d = x.shape
+        k = w_u.shape[1]
+        y = torch.empty_like(x)
+        h_u, h_i = torch.zeros_like(w_u), torch.zeros_like(w_i)
+        if n > 0:                                                # (an empty tensor has no address to hand over)
+            lib = _lib.load()
+            ws = torch.empty(lib.sslrec_hyper_ws_bytes(n, n_split, d, k) // 4 + 1, dtype=torch.float32, device=x.device)
+            rc = lib.sslrec_hyper_fwd_f32(x.data_ptr(), e.data_ptr(), n, n_split, d, w_u.data_ptr(), w_i.data_ptr(), k, mult, leaky, keep_rate,
+                                          _ptr(state), stream, h_u.data_ptr(), h_i.data_ptr(), y.data_ptr(), ws.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_hyper_fwd_f32')
+        ctx.args = (n_split, mult, leaky, keep_rate, stream)
+        ctx.state = state
+        ctx.save_for_backward(x, e, w_u, w_i, y, h_u, h_i)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, e, w_u, w_i, y, h_u, h_i = ctx.saved_tensors
+        n_split, mult, leaky, keep_rate, stream = ctx.args
+        gy = _f32c(gy)
+        n, d = x.shape
+        k = w_u.shape[1]
+        dx, de = torch.empty_like(x), torch.empty_like(e)
+        dw_u, dw_i = torch.empty_like(w_u), torch.empty_like(w_i)
+        if n == 0:
+            return dx, de, None, dw_u.zero_(), dw_i.zero_(), None, None, None, None, None
+        lib = _lib.load()
+        ws = torch.empty(lib.sslrec_hyper_ws_bytes(n, n_split, d, k) // 4 + 1, dtype=torch.float32, device=x.device)
+        rc = lib.sslrec_hyper_bwd_f32(x.data_ptr(), e.data_ptr(), gy.data_ptr(), y.data_ptr(), n, n_split, d, w_u.data_ptr(), w_i.data_ptr(),
+                                      h_u.data_ptr(), h_i.data_ptr(), k, mult, leaky, keep_rate, _ptr(ctx.state), stream, dx.data_ptr(),
+                                      de.data_ptr(), dw_u.data_ptr(), dw_i.data_ptr(), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_hyper_bwd_f32')
+        return dx, de, None, dw_u, dw_i, None, None, None, None, None
+
+
+def hyper_propagate_stacked(x, e, n_user, user_hyper, item_hyper, mult, leaky, keep_rate, rng=None):
+    """One hypergraph layer of HCCF on the stacked tables x, e = [U; I] [N, d] (hccf.py:43-44, 48-49, 105-107): with
+    A = dropout(e_r @ W_r * mult, p = 1 - keep_rate), W_r = user_hyper for the first n_user rows and item_hyper for the rest ([d, K]),
+    returns concat over the two ranges of act(A @ act(A.T @ x_r)), act = LeakyReLU(leaky).  Differentiable in x, e and both matrices;
+    no [N, K] tensor forward or backward.  rng = (rng.PhiloxState, stream): the dropout mask is computed in the kernels from that
+    call's Philox stream (hyper_keep_mask writes the same mask out); required when keep_rate < 1.  The backward recomputes the mask from
+    the LIVE state tensor, not from a snapshot: the state must not advance() between this call and its backward (a training step
+    advances once, before its forward), or the gradients belong to another mask.  Embedding sizes without a kernel
+    are zero-padded; a shape that does not fit LDS (hyper_fused_ok) runs the composed torch expression with the same mask."""
+    _need_gpu(x, e, user_hyper, item_hyper)
+    n_user, mult, leaky, keep_rate = int(n_user), float(mult), float(leaky), float(keep_rate)
+    if not leaky > 0.0:
+        raise ValueError('hyper_propagate_stacked: leaky must be positive (the backward reads the slope from the sign of the output), got %r' % leaky)
+    if not 0.0 < keep_rate <= 1.0:
+        raise ValueError('hyper_propagate_stacked: keep_rate must lie in (0, 1], got %r' % keep_rate)
+    if x.dim() != 2 or e.shape != x.shape or not 0 <= n_user <= x.shape[0] or user_hyper.dim() != 2 or user_hyper.shape != item_hyper.shape \
+            or user_hyper.shape[0] != x.shape[1] or not 1 <= user_hyper.shape[1] <= HYPER_KMAX:
+        raise ValueError('hyper_propagate_stacked: tables %s / %s, n_user %d, matrices %s / %s ([d, K], 1 <= K <= %d)' %
+                         (tuple(x.shape), tuple(e.shape), n_user, tuple(user_hyper.shape), tuple(item_hyper.shape), HYPER_KMAX))
+    state, stream = None, 0
+    if keep_rate < 1.0:
+        if rng is None:
+            raise ValueError('hyper_propagate_stacked: keep_rate < 1 needs rng = (PhiloxState, stream)')
+        state, stream = rng[0].state, int(rng[1])
+    d, k = x.shape[1], user_hyper.shape[1]
+    dp = _padded_dim(d, HYPER_DIMS)
+    if not hyper_fused_ok(dp, k):
+        mask = None if state is None else hyper_keep_mask(rng[0], stream, x.shape[0], k, keep_rate)
+        return _hyper_composed(x, e, n_user, user_hyper, item_hyper, mult, leaky, keep_rate, mask)
+    pad_rows = lambda w: w if dp == d else torch.nn.functional.pad(w, (0, 0, 0, dp - d))
+    y = _HyperFn.apply(_pad_cols(x, dp), _pad_cols(e, dp), n_user, pad_rows(user_hyper), pad_rows(item_hyper), mult, leaky, keep_rate, state,
+                       stream)
+    return y if dp == d else y[:, :d]
+
+
+# ----------------------------------------------------------------------------------------------
 # fused L-layer propagation + layer SUM (+ optional per-layer perturbation)
 #   S = E0 + sum_l E_l,  E_l = P_l(A E_{l-1})      (lightgcn.py:31-43 / simgcl.py:20-30)
 # backward:  g_L = G,  g_{l-1} = G + A^T g_l,  dE0 = g_0   (perturbation has unit Jacobian a.e.)

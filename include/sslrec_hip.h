@@ -717,6 +717,33 @@ int sslrec_hyper_bwd_f32(const float *X, const float *E, const float *dY, const 
                          float keep_rate, const uint64_t *philox_state, uint32_t philox_stream, float *dX, float *dE, float *dW_u,
                          float *dW_i, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * Graph-transformer layer of AutoCF / GFormer (csrc/gt.hip), GTLayer.forward of models/general_cf/autocf.py:109-129 (verbatim again in
+ * gformer.py:221-255):
+ *     qEmbeds = (embeds[rows] @ self.qTrans).view([-1, head_num, d // head_num])        (kEmbeds, vEmbeds from embeds[cols])
+ *     att = t.clamp(t.einsum('ehd, ehd -> eh', qEmbeds, kEmbeds), -10.0, 10.0);  expAtt = t.exp(att)
+ *     att = expAtt / (tem.index_add_(0, rows, expAtt)[rows] + 1e-8)
+ *     resEmbeds = tem.index_add_(0, rows, t.einsum('eh, ehd -> ehd', att, vEmbeds).view([-1, d]))
+ * with the projections hoisted to the nodes ((X[rows]) W = (X W)[rows]): Q, K, V [n, d] fp32 row-major are the projected NODE tables,
+ * the pattern is square (n x n), WITHOUT duplicate entries, given as CSR (rowptr [n + 1], col [E]: column of every entry, rows in
+ * order) and, for the backward, as CSC (colptr [n + 1], row [E]).  d in {32, 64, 128}, heads dividing d with d / heads in
+ * {4, 8, 16, 32, 64, 128}.  long_rows / long_cols (n_long / n_long_cols of them, nullable when 0): the rows / columns of more than
+ * SSLREC_EDGE_LONG_ROW entries, which get a workgroup each.  Nothing of size E x d or E x heads is written; no atomics, every sum in a
+ * fixed order: two runs give the same bits.  SSLREC_E_BADARG before any launch for a null required pointer or a shape outside these
+ * ranges; n == 0 returns 0 without a launch. */
+
+/* Y [n, d] = sum over the row's entries of exp(clamp(<Q[r, h], K[c, h]>, -10, 10)) / (Z[r, h] + 1e-8) * V[c, h]; rows without entries are
+ * exact zeros.  Z [n, heads] receives the row sums of the exponentials, which the backward needs together with Y. */
+int sslrec_gt_fwd_f32(const int32_t *rowptr, const int32_t *col, int32_t n, const int32_t *long_rows, int32_t n_long, const float *Q,
+                      const float *K, const float *V, int32_t d, int32_t heads, float *Y, float *Z, void *stream);
+
+/* From dY [n, d] and the forward's Y, Z (autograd of the lines above): dQ, dK, dV [n, d], each nullable (not computed).  t_ws: n * heads
+ * floats of device memory, contents irrelevant on entry (t[i, h] = <dY[i, h], Y[i, h]>, the row sums of a * da). */
+int sslrec_gt_bwd_f32(const int32_t *rowptr, const int32_t *col, const int32_t *long_rows, int32_t n_long, const int32_t *colptr,
+                      const int32_t *row, const int32_t *long_cols, int32_t n_long_cols, int32_t n, const float *Q, const float *K,
+                      const float *V, const float *Y, const float *Z, const float *dY, int32_t d, int32_t heads, float *dQ, float *dK,
+                      float *dV, float *t_ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

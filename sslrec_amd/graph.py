@@ -633,3 +633,87 @@ def graph_of(adj):
         except Exception:       # an object that cannot carry attributes: rebuilt on every call
             pass
     return g
+
+
+class EdgePattern:
+    """Sparsity pattern of a square N x N matrix WITHOUT duplicate entries, for the per-entry kernels that walk it by rows and by
+    columns (csrc/gt.hip: ops.edge_attention): device int32 `rowptr` [N + 1] / `col` [E] (CSR, entries sorted by row, then column),
+    `colptr` [N + 1] / `row` [E] (the same entries sorted by column, then row) and `long_rows` / `long_cols`, the rows / columns of
+    more than EDGE_LONG_ROW entries.  Built ON THE DEVICE with torch ops from COO indices in any order (AutoCF builds a new decoder
+    graph every `fix_steps` steps: no host round trip of the entries).  Keys row * N + col that already increase strictly -- the
+    output of `t.unique(row * N + col)`, as the decoder graph is made -- skip the sort and the duplicate test (`fast_path`: None =
+    take it when the keys allow, False = never; `took_fast_path` tells).  Costs one host synchronisation for the checks and one
+    for the long-row counts."""
+
+    def __init__(self, rows, cols, n, fast_path=None):
+        n = int(n)
+        if not (torch.is_tensor(rows) and torch.is_tensor(cols)) or not rows.is_cuda or not cols.is_cuda:
+            raise RuntimeError('EdgePattern is built on a HIP device only (got %s indices); there is no CPU fallback by design' %
+                               (rows.device if torch.is_tensor(rows) else type(rows).__name__))
+        if rows.dim() != 1 or rows.shape != cols.shape:
+            raise ValueError('EdgePattern: rows and cols must be 1-d index tensors of one length, got %s / %s' % (tuple(rows.shape), tuple(cols.shape)))
+        if not 0 <= n < 2 ** 31 - 1:
+            raise ValueError('EdgePattern: N = %d exceeds int32 indexing' % n)
+        if rows.numel() >= 2 ** 31 - 1:
+            raise ValueError('EdgePattern: %d entries exceed int32 indexing' % rows.numel())
+        rows, cols = rows.long(), cols.long()
+        dev = rows.device
+        self.n, self.nnz, self.device = n, int(rows.numel()), dev
+        self.shape = (n, n)
+        key = rows * n + cols
+        if self.nnz:
+            increasing = (key[1:] > key[:-1]).all()
+            in_range = (rows.min() >= 0) & (rows.max() < n) & (cols.min() >= 0) & (cols.max() < n)
+            increasing, in_range = (bool(x) for x in torch.stack([increasing, in_range]).tolist())
+            if not in_range:
+                raise ValueError('EdgePattern: an index lies outside [0, %d)' % n)
+        else:
+            increasing = True
+        self.took_fast_path = bool(increasing and fast_path is not False)
+        if not self.took_fast_path:
+            key = torch.sort(key)[0]
+            if self.nnz and bool((key[1:] == key[:-1]).any()):
+                raise ValueError('EdgePattern: the pattern has a duplicate entry (coalesce it first: the edge attention counts '
+                                 'every entry once)')
+        r, c = key // n, key % n
+        key_t = torch.sort(c * n + r)[0]
+        deg_r = torch.bincount(r, minlength=n) if self.nnz else torch.zeros(n, dtype=torch.int64, device=dev)
+        deg_c = torch.bincount(c, minlength=n) if self.nnz else torch.zeros(n, dtype=torch.int64, device=dev)
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.rowptr = torch.cat([zero, deg_r.cumsum(0)]).to(torch.int32)
+        self.colptr = torch.cat([zero, deg_c.cumsum(0)]).to(torch.int32)
+        self.col = c.to(torch.int32)
+        self.row = (key_t % n).to(torch.int32)
+        self.long_rows = torch.nonzero(deg_r > EDGE_LONG_ROW).view(-1).to(torch.int32)
+        self.long_cols = torch.nonzero(deg_c > EDGE_LONG_ROW).view(-1).to(torch.int32)
+        self._coo = None
+
+    def coo(self):
+        """(rows, cols) int64 in CSR order, for the composed torch expression of shapes without a kernel"""
+        if self._coo is None:
+            deg = (self.rowptr[1:] - self.rowptr[:-1]).long()
+            self._coo = (torch.repeat_interleave(torch.arange(self.n, device=self.device), deg), self.col.long())
+        return self._coo
+
+    @classmethod
+    def from_torch_sparse(cls, adj, device=None):
+        idx = adj._indices()
+        if device is not None:
+            idx = idx.to(device)
+        if adj.shape[0] != adj.shape[1]:
+            raise ValueError('EdgePattern: a square adjacency expected, got %s' % (tuple(adj.shape),))
+        return cls(idx[0], idx[1], adj.shape[0])
+
+
+def pattern_of(adj):
+    """EdgePattern of a torch sparse adjacency, built once and cached ON the tensor object (like graph_of)"""
+    if isinstance(adj, EdgePattern):
+        return adj
+    p = getattr(adj, '_sslrec_pattern', None)
+    if p is None:
+        p = EdgePattern.from_torch_sparse(adj)
+        try:
+            adj._sslrec_pattern = p
+        except Exception:
+            pass
+    return p

@@ -19,7 +19,7 @@ class GraphCF(BaseModel):
         super().__init__(data_handler)
         self.adj = data_handler.torch_adj
         model_cfg = configs['model']
-        self.layer_num = model_cfg['layer_num']
+        self.layer_num = model_cfg.get('layer_num')      # (AutoCF names its depths gcn_layer / gt_layer and has no layer_num)
         self.reg_weight = model_cfg['reg_weight']
         xavier = nn.init.xavier_uniform_
         # The two parameters are adjacent row ranges of ONE buffer -- [user_embeds; item_embeds], the table the propagation works on

@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from .graph import BundledLayout, DroppedView, PropGraph, RevaluedView, graph_of
+from .graph import BundledLayout, DroppedView, EdgePattern, PropGraph, RevaluedView, graph_of, pattern_of
 
 # When set to a list, every SpMM launch appends (start_event, end_event, plan, d, has_acc): the
 # measurement hook bench.py uses to time the dominant kernel with HIP events on the launch stream.
@@ -803,6 +803,95 @@ def hyper_propagate_stacked(x, e, n_user, user_hyper, item_hyper, mult, leaky, k
     y = _HyperFn.apply(_pad_cols(x, dp), _pad_cols(e, dp), n_user, pad_rows(user_hyper), pad_rows(item_hyper), mult, leaky, keep_rate, state,
                        stream)
     return y if dp == d else y[:, :d]
+
+
+# ----------------------------------------------------------------------------------------------
+# graph-transformer layer of AutoCF / GFormer (autocf.py:109-129) on projected NODE tables: an edge attention over a sparse pattern,
+# nothing of size E x d or E x H stored forward or backward, no atomics (csrc/gt.hip)
+# ----------------------------------------------------------------------------------------------
+GT_DIMS = (32, 64, 128)
+GT_HEAD_DIMS = (4, 8, 16, 32, 64, 128)
+
+
+def edge_attention_fused_ok(d, head_num):
+    """whether csrc/gt.hip has kernels for embedding size d with head_num heads; other shapes run the composed torch expression"""
+    return d in GT_DIMS and d % head_num == 0 and d // head_num in GT_HEAD_DIMS
+
+
+def _edge_attention_composed(pattern, q, k, v, head_num):
+    """the reference's expression (autocf.py:119-128) on the node tables: [E, d] intermediates and index_add_"""
+    n, d = q.shape
+    rows, cols = pattern.coo()
+    dh = d // head_num
+    qe, ke, ve = (x.view(-1, head_num, dh) for x in (q[rows], k[cols], v[cols]))
+    att = torch.exp(torch.clamp(torch.einsum('ehd, ehd -> eh', qe, ke), -10.0, 10.0))
+    norm = torch.zeros(n, head_num, dtype=q.dtype, device=q.device).index_add_(0, rows, att)[rows]
+    att = att / (norm + 1e-8)
+    res = torch.einsum('eh, ehd -> ehd', att, ve).reshape(-1, d)
+    return torch.zeros(n, d, dtype=q.dtype, device=q.device).index_add_(0, rows, res)
+
+
+class _EdgeAttentionFn(torch.autograd.Function):
+    """saves Q, K, V, Y and Z ([N, H]: the row sums of the exponentials); the backward recomputes every score"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, pattern, head_num):
+        q, k, v = _f32c(q), _f32c(k), _f32c(v)
+        n, d = q.shape
+        y = torch.empty_like(q)
+        z = torch.empty(n, head_num, dtype=torch.float32, device=q.device)
+        if n > 0:                                                # (an empty tensor has no address to hand over)
+            p = pattern
+            rc = _lib.load().sslrec_gt_fwd_f32(p.rowptr.data_ptr(), p.col.data_ptr(), n, _ptr(p.long_rows) if p.long_rows.numel() else None,
+                                               p.long_rows.numel(), q.data_ptr(), k.data_ptr(), v.data_ptr(), d, head_num, y.data_ptr(),
+                                               z.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_gt_fwd_f32')
+        ctx.pattern, ctx.head_num = pattern, head_num
+        ctx.save_for_backward(q, k, v, y, z)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        q, k, v, y, z = ctx.saved_tensors
+        p, head_num = ctx.pattern, ctx.head_num
+        gy = _f32c(gy)
+        n, d = q.shape
+        dq, dk, dv = (torch.empty_like(q) if need else None for need in ctx.needs_input_grad[:3])
+        if n > 0 and (dq is not None or dk is not None or dv is not None):
+            t_ws = torch.empty(n * head_num, dtype=torch.float32, device=q.device)
+            rc = _lib.load().sslrec_gt_bwd_f32(p.rowptr.data_ptr(), p.col.data_ptr(), _ptr(p.long_rows) if p.long_rows.numel() else None,
+                                               p.long_rows.numel(), p.colptr.data_ptr(), p.row.data_ptr(),
+                                               _ptr(p.long_cols) if p.long_cols.numel() else None, p.long_cols.numel(), n, q.data_ptr(),
+                                               k.data_ptr(), v.data_ptr(), y.data_ptr(), z.data_ptr(), gy.data_ptr(), d, head_num, _ptr(dq) or None,
+                                               _ptr(dk) or None, _ptr(dv) or None, t_ws.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_gt_bwd_f32')
+        return dq, dk, dv, None, None
+
+
+def edge_attention(pattern, q, k, v, head_num):
+    """Y [N, d] of the graph-transformer layer (autocf.py:109-129, gformer.py:221-255) from the projected NODE tables q, k, v [N, d]
+    (the reference projects the [E, d] gathers; (X[rows]) W = (X W)[rows]): per entry e = (r, c) of `pattern` and head h,
+    a = exp(clamp(<q[r, h], k[c, h]>, -10, 10)) / (sum of the exponentials over row r + 1e-8), Y[r, h] = sum over the row of a * v[c, h];
+    rows without entries are exact zeros.  `pattern`: a graph.EdgePattern (square, no duplicate entries) or a torch sparse adjacency
+    (its pattern is built once and cached on the tensor).  Differentiable in q, k, v; nothing of size E x d or E x H is stored and two
+    runs give the same bits.  d in {32, 64, 128} with d / head_num in {4, ..., 128} run csrc/gt.hip; any other shape runs the composed
+    torch expression (edge_attention_fused_ok)."""
+    _need_gpu(q, k, v)
+    if not isinstance(pattern, EdgePattern):
+        pattern = pattern_of(pattern)
+    head_num = int(head_num)
+    if q.dim() != 2 or q.shape != k.shape or q.shape != v.shape or q.shape[0] != pattern.n:
+        raise ValueError('edge_attention: tables %s / %s / %s for a pattern of %d nodes' % (tuple(q.shape), tuple(k.shape), tuple(v.shape), pattern.n))
+    d = q.shape[1]
+    if head_num < 1 or d % head_num != 0:
+        raise ValueError('edge_attention: the embedding size %d is not a multiple of head_num = %d' % (d, head_num))
+    dev = q.device
+    if pattern.device.type != dev.type or (pattern.device.index is not None and dev.index is not None and pattern.device.index != dev.index):
+        raise ValueError('edge_attention: the pattern lives on %s, the tensors on %s' % (pattern.device, dev))
+    q, k, v = (x.float().contiguous() for x in (q, k, v))
+    if not edge_attention_fused_ok(d, head_num):
+        return _edge_attention_composed(pattern, q, k, v, head_num)
+    return _EdgeAttentionFn.apply(q, k, v, pattern, head_num)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -329,3 +329,65 @@ class Trainer(object):
         model.load_state_dict(torch.load(path))
         self.logger.log('Load model parameters from {}'.format(path))
         return model
+
+
+class AutoCFTrainer(Trainer):
+    """reference trainer/trainer.py:201-250: every `model.fix_steps` steps the model samples seeds (`sample_subgraphs`) and masks their
+    subgraphs (`mask_subgraphs`); those steps add -sampScores.mean() as `infomax_loss`.  The batches come from the default stream.
+    As in `_train_epoch_eager`, the step's 0-d tensors are read once at the end of the epoch and summed on the host in the
+    reference's order.  train.hip_graph is refused: the resampling steps draw on the host and build a new graph, which a captured
+    step cannot do.  train.host_rng_replay is OFF for this trainer: the model's draws (t.rand / t.randint in LocalGraph and the
+    masker) go to the CPU generator directly, which the replay would have to hand back around every resampling."""
+
+    def __init__(self, data_handler, logger):
+        super().__init__(data_handler, logger)
+        self.fix_steps = configs['model']['fix_steps']
+        if configs['train'].get('hip_graph'):
+            raise NotImplementedError('train.hip_graph is not supported by AutoCFTrainer: every model.fix_steps steps the step draws on '
+                                      'the host and rebuilds its graphs')
+
+    @log_exceptions
+    def train(self, model):
+        from .. import rng
+        if rng.active_host_replay(self._device_of(model)) is not None:
+            raise RuntimeError('AutoCFTrainer draws from the CPU generator directly: disable the host generator replay '
+                               '(train.host_rng_replay) before training AutoCF')
+        return self._train(model)
+
+    def train_epoch(self, model, epoch_idx):
+        loader = self.data_handler.train_dataloader
+        loader.dataset.sample_negs()
+        n_batches = len(loader)
+        model.train()
+        kept = []
+        encoder_adj = decoder_adj = None
+        for i, tem in enumerate(loader):
+            self.optimizer.zero_grad()
+            batch_data = [x.long().to(configs['device']) for x in tem]
+            resample = i % self.fix_steps == 0
+            if resample:
+                samp_scores, seeds = model.sample_subgraphs()
+                encoder_adj, decoder_adj = model.mask_subgraphs(seeds)
+            loss, loss_dict = model.cal_loss(batch_data, encoder_adj, decoder_adj)
+            if resample:
+                infomax = -samp_scores.mean()
+                loss = loss + infomax
+                loss_dict['infomax_loss'] = infomax
+            self._backward(loss)
+            self.optimizer.step()
+            kept.append((loss.detach().reshape(()), {k: (v.detach().reshape(()).to(loss.dtype) if torch.is_tensor(v)
+                                                         else torch.tensor(float(v), dtype=loss.dtype, device=loss.device))
+                                                     for k, v in loss_dict.items()}))
+        loss_log, ep_loss = {}, 0.0
+        if kept:
+            flat = torch.stack([x for loss, parts in kept for x in [loss] + list(parts.values())]).double().cpu().tolist()      # one synchronisation per epoch
+            pos = 0
+            for _, parts in kept:
+                ep_loss += flat[pos]
+                for j, name in enumerate(parts):
+                    loss_log[name] = loss_log.get(name, 0.0) + flat[pos + 1 + j] / n_batches
+                pos += 1 + len(parts)
+        self.step_losses = [sorted(parts) for _, parts in kept]          # names logged by every step of the last epoch
+        steps = max(1, len(loader.dataset) // configs['train']['batch_size'])
+        writer.add_scalar('Loss/train', ep_loss / steps, epoch_idx)
+        self.logger.log_loss(epoch_idx, loss_log, save_to_log=bool(configs['train']['log_loss']))

@@ -744,6 +744,38 @@ int sslrec_gt_bwd_f32(const int32_t *rowptr, const int32_t *col, const int32_t *
                       const float *V, const float *Y, const float *Z, const float *dY, int32_t d, int32_t heads, float *dQ, float *dK,
                       float *dV, float *t_ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * Alignment + uniformity loss of DirectAU (csrc/au.hip), models/loss_utils.py:75-86 at the call site models/general_cf/directau.py:42-47:
+ *     anc_embeds = user_embeds[ancs];  pos_embeds = item_embeds[poss]
+ *     align_loss = alignment(anc_embeds, pos_embeds)          x, y = F.normalize(x, dim=-1), F.normalize(y, dim=-1)
+ *                                                              (x - y).norm(p=2, dim=1).pow(alpha).mean()                 (alpha = 2)
+ *     uniform_loss = gamma * (uniformity(anc_embeds) + uniformity(pos_embeds)) / 2
+ *                                                              t.pdist(F.normalize(x, dim=-1), p=2).pow(2).mul(-2).exp().mean().log()
+ *     loss = align_loss + uniform_loss
+ * on the stacked table T [N, d] fp32 row-major: row anc of the first n_user rows and row n_user + pos, both multiplied by `scale`
+ * (directau.py:35 averages the layers: T is their SUM and scale = 1 / (L + 1)).  ancs, poss: int64 [B], duplicates welcome; an index
+ * outside its part of the table contributes a zero row and receives no gradient.  d in {32, 64, 128}, 2 <= B <= 8192,
+ * 0 <= n_user <= N, scale and gamma finite.  terms: bit 0 the alignment, bit 1 the uniformity of the anchors, bit 2 that of the
+ * positives (1 .. 7; DirectAU: 7; a term left out is 0 in the sums above).  Nothing of size B x B or B (B - 1) / 2 is written; a pair
+ * is left out when its two batch POSITIONS are equal, never by value; no float atomics, every sum in a fixed order: two runs give the
+ * same bits.  SSLREC_E_BADARG before any launch for a null pointer or a value outside these ranges. */
+
+/* bytes of the workspace both calls share (normalised rows, norms, per-split partial sums, staged gradient rows, scatter table);
+ * 0 for arguments out of range */
+size_t sslrec_au_ws_bytes(int32_t B, int32_t d);
+
+/* out[0..2] = loss, align_loss, uniform_loss (directau.py:45-47); out[3..4] = the two sums over pairs, which the backward needs
+ * (out: 8 floats of device memory).  ws: contents irrelevant on entry; the backward reads what this call leaves there. */
+int sslrec_au_fwd_f32(const float *T, int32_t N, int32_t n_user, int32_t d, const int64_t *ancs, const int64_t *poss, int32_t B, float scale,
+                      float gamma, int32_t terms, float *out, void *ws, void *stream);
+
+/* Autograd of the lines above plus the index_put backward of both gathers (directau.py:43-44) in one call: with the SAME arguments,
+ * `out` and `ws` as the forward left them, dT [N, d] (zero-initialised or already holding gradients) receives
+ * g_align[0] * d align_loss / dT + g_uniform[0] * d uniform_loss / dT (device scalars; the same address for both is the gradient of
+ * `loss`).  Rows that share a destination are added in ascending batch position. */
+int sslrec_au_bwd_f32(int32_t N, int32_t n_user, int32_t d, const int64_t *ancs, const int64_t *poss, int32_t B, float scale, float gamma,
+                      int32_t terms, const float *out, const float *g_align, const float *g_uniform, float *dT, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,9 @@ SIGNATURES = {
     'sslrec_hyper_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _F, _F, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     'sslrec_gt_fwd_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     'sslrec_gt_bwd_f32': (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'sslrec_au_ws_bytes': (C.c_size_t, [_I, _I]),
+    'sslrec_au_fwd_f32': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _I, _P, _P, _P]),
+    'sslrec_au_bwd_f32': (C.c_int, [_I, _I, _I, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -20,7 +20,7 @@ class GraphCF(BaseModel):
         self.adj = data_handler.torch_adj
         model_cfg = configs['model']
         self.layer_num = model_cfg.get('layer_num')      # (AutoCF names its depths gcn_layer / gt_layer and has no layer_num)
-        self.reg_weight = model_cfg['reg_weight']
+        self.reg_weight = model_cfg.get('reg_weight')    # (DirectAU has no regularizer term: its weight decay is the optimizer's)
         xavier = nn.init.xavier_uniform_
         # The two parameters are adjacent row ranges of ONE buffer -- [user_embeds; item_embeds], the table the propagation works on
         # (reference lightgcn.py:34 concatenates them in every forward) -- initialised in the reference's order with the reference's

@@ -1,10 +1,10 @@
 """Loss library of the hot path, same names / signatures / return conventions as the
 reference's models/loss_utils.py (cal_bpr_loss :7-10, reg_pick_embeds :13-17, reg_params
-:20-24, cal_infonce_loss :30-39, cal_infonce_loss_spec_nodes :42-51), backed by the fused HIP kernels of sslrec_amd.ops.
+:20-24, cal_infonce_loss :30-39, cal_infonce_loss_spec_nodes :42-51, alignment :75-79, uniformity :82-86), backed by the fused HIP kernels of sslrec_amd.ops.
 
 `cal_*_gathered` are the table-level forms the in-tree models use: they take the full
 embedding tables plus the batch indices, so the [B, d] gathers of lightgcn.py:49-51 /
-simgcl.py:32-37 are never materialized.  The other seven functions of the upstream file
+simgcl.py:32-37 are never materialized.  The other five functions of the upstream file
 belong to models outside this path's scope and are not provided.
 """
 from .. import ops
@@ -60,6 +60,23 @@ def cal_infonce_loss_spec_nodes(embeds1, embeds2, nodes, temp, precision=None):
     normed1 = F.normalize(embeds1 + 1e-8, p=2)
     normed2 = F.normalize(embeds2 + 1e-8, p=2)
     return ops.infonce_loss_gathered(normed1, normed2, nodes, temp, variant=0, precision=precision) / nodes.shape[0]
+
+
+def alignment(x, y, alpha=2):
+    """mean_b |x^_b - y^_b|^alpha with x^ = F.normalize(x) (loss_utils.py:75-79) for dense [B, d] rows: the fused kernels of
+    csrc/au.hip with identity indices; alpha != 2 runs the reference's expression"""
+    return ops.alignment(x, y, alpha)
+
+
+def uniformity(x):
+    """log mean over the B (B - 1) / 2 pairs of exp(-2 |x^_i - x^_j|^2) (loss_utils.py:82-86) without the pair vector"""
+    return ops.uniformity(x)
+
+
+def cal_align_uniform_loss_stacked(stacked_embeds, user_num, ancs, poss, gamma, scale=1.0):
+    """(loss, align_loss, uniform_loss) of directau.py:43-47 on the stacked [users; items] table: gathers, both losses and their sum
+    as one autograd node; `scale` multiplies the gathered rows (the mean over the layers when the table is their sum)"""
+    return ops.align_uniform_loss_stacked(stacked_embeds, user_num, ancs, poss, gamma, scale)
 
 
 def reg_pick_embeds(embeds_list):

@@ -1569,6 +1569,130 @@ def infonce_loss_two_sided(stacked1, stacked2, n_user, user_idx, item_idx, temp=
 
 
 # ----------------------------------------------------------------------------------------------
+# alignment + uniformity loss of DirectAU (loss_utils.py:75-86, directau.py:42-47) on the stacked table: gathers, both normalisations,
+# the B x B Gaussian pair sums and the index_put backward as one autograd node, nothing of size B^2 stored (csrc/au.hip)
+# ----------------------------------------------------------------------------------------------
+AU_DIMS = (32, 64, 128)
+AU_MAX_BATCH = 8192          # 2 B gathered rows must fit the deterministic scatter's table
+AU_ALIGN, AU_UNIFORM_ANC, AU_UNIFORM_POS = 1, 2, 4
+
+
+def _au_uniformity(x):
+    """loss_utils.py:82-86"""
+    x = torch.nn.functional.normalize(x, dim=-1)
+    return torch.pdist(x, p=2).pow(2).mul(-2).exp().mean().log()
+
+
+def _au_alignment(x, y, alpha=2):
+    """loss_utils.py:75-79"""
+    x, y = torch.nn.functional.normalize(x, dim=-1), torch.nn.functional.normalize(y, dim=-1)
+    return (x - y).norm(p=2, dim=1).pow(alpha).mean()
+
+
+def _au_composed(table, n_user, ancs, poss, gamma, scale):
+    """the reference's expression (directau.py:35, 43-47) on the layer sum"""
+    anc, pos = table[:n_user][ancs] * scale, table[n_user:][poss] * scale
+    align = _au_alignment(anc, pos)
+    uniform = gamma * (_au_uniformity(anc) + _au_uniformity(pos)) / 2
+    return align + uniform, align, uniform
+
+
+class _AlignUniformFn(torch.autograd.Function):
+    """outputs (loss, align_loss, uniform_loss) from one 5-float result; keeps the workspace (normalised rows, norms) for the backward,
+    which recomputes the pair terms and scatters both gathers' gradients into one [N, d] buffer"""
+
+    @staticmethod
+    def forward(ctx, table, n_user, ancs, poss, gamma, scale, terms):
+        table = _f32c(table)
+        ia, ip = _idx(ancs), _idx(poss)
+        n, d = table.shape
+        B = int(ia.numel())
+        lib = _lib.load()
+        ws = torch.empty(lib.sslrec_au_ws_bytes(B, d) // 4 + 1, dtype=torch.float32, device=table.device)
+        out = torch.empty(8, dtype=torch.float32, device=table.device)
+        rc = lib.sslrec_au_fwd_f32(table.data_ptr(), n, n_user, d, ia.data_ptr(), ip.data_ptr(), B, scale, gamma, terms, out.data_ptr(),
+                                   ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_au_fwd_f32')
+        ctx.save_for_backward(ia, ip, out)
+        ctx.ws = ws
+        ctx.meta = (n, d, B, n_user, gamma, scale, terms)
+        ctx.set_materialize_grads(False)
+        return out[0].reshape(()), out[1].reshape(()), out[2].reshape(())
+
+    @staticmethod
+    def backward(ctx, g_loss, g_align, g_uniform):
+        ia, ip, out = ctx.saved_tensors
+        n, d, B, n_user, gamma, scale, terms = ctx.meta
+        both = lambda a, b: a if b is None else (b if a is None else a + b)
+        ga, gu = both(g_loss, g_align), both(g_loss, g_uniform)       # loss = align + uniform: the usual call has g_loss alone
+        if ga is None and gu is None:
+            return None, None, None, None, None, None, None
+        as_dev = lambda g: torch.zeros(1, dtype=torch.float32, device=out.device) if g is None else g.reshape(1).to(torch.float32).contiguous()
+        ga = as_dev(ga)
+        gu = ga if gu is g_loss and g_align is None else as_dev(gu)
+        grad = torch.zeros(n, d, dtype=torch.float32, device=out.device)
+        lib = _lib.load()
+        rc = lib.sslrec_au_bwd_f32(n, n_user, d, ia.data_ptr(), ip.data_ptr(), B, scale, gamma, terms, out.data_ptr(), ga.data_ptr(),
+                                   gu.data_ptr(), grad.data_ptr(), ctx.ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_au_bwd_f32')
+        return grad, None, None, None, None, None, None
+
+
+def _au_fused(table, n_user, ancs, poss, gamma, scale, terms):
+    d = table.shape[1]
+    return _AlignUniformFn.apply(_pad_cols(table, _padded_dim(d, AU_DIMS)), n_user, ancs, poss, gamma, scale, terms)
+
+
+def align_uniform_loss_stacked(table, n_user, ancs, poss, gamma, scale=1.0):
+    """(loss, align_loss, uniform_loss) of DirectAU (directau.py:43-47, loss_utils.py:75-86) on the stacked table [users; items] [N, d]:
+    with x = normalize(scale * table[ancs]) and y = normalize(scale * table[n_user + poss]),
+        align_loss = mean |x - y|^2,  uniform_loss = gamma * (uniformity(x) + uniformity(y)) / 2,  loss = their sum
+    as ONE autograd node returning three 0-d tensors; the gradient reaches `table` only.  `scale` folds the mean over the layers
+    (directau.py:35) into the gather: pass the layer SUM of ops.propagate_sum and scale = 1 / (L + 1).  No [B, B] or [B (B - 1) / 2]
+    tensor forward or backward; duplicated indices are ordinary pairs (a pair is left out by batch position only); two runs give the
+    same bits.  Embedding sizes without a kernel are zero-padded.  What the kernels do not cover runs the reference's torch
+    expression: B < 2 or an empty table (NaN, as the mean of an empty pdist is), B > 8192, d > 128."""
+    _need_gpu(table, ancs, poss)
+    n_user, gamma, scale = int(n_user), float(gamma), float(scale)
+    if table.dim() != 2 or ancs.dim() != 1 or poss.dim() != 1 or tuple(ancs.shape) != tuple(poss.shape) or not 0 <= n_user <= table.shape[0]:
+        raise ValueError('align_uniform_loss_stacked: table %s, n_user %d, ancs %s, poss %s ([N, d], 0 <= n_user <= N, two [B] index vectors)'
+                         % (tuple(table.shape), n_user, tuple(ancs.shape), tuple(poss.shape)))
+    if gamma != gamma or scale != scale or abs(gamma) == float('inf') or abs(scale) == float('inf'):
+        raise ValueError('align_uniform_loss_stacked: gamma and scale must be finite, got %r and %r' % (gamma, scale))
+    B = int(ancs.shape[0])
+    if B < 2 or B > AU_MAX_BATCH or table.shape[0] == 0 or table.shape[1] == 0 or table.shape[1] > AU_DIMS[-1]:
+        return _au_composed(table, n_user, ancs.long(), poss.long(), gamma, scale)
+    return _au_fused(table, n_user, ancs, poss, gamma, scale, AU_ALIGN | AU_UNIFORM_ANC | AU_UNIFORM_POS)
+
+
+def _au_dense_ok(x):
+    return 2 <= x.shape[0] <= AU_MAX_BATCH and 1 <= x.shape[1] <= AU_DIMS[-1]
+
+
+def alignment(x, y, alpha=2):
+    """loss_utils.alignment (loss_utils.py:75-79) for dense [B, d] rows on the device: the fused kernels with identity indices over
+    [x; y]; alpha != 2 and shapes without a kernel run the reference's expression"""
+    _need_gpu(x, y)
+    if x.dim() != 2 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError('alignment: two [B, d] tensors of one shape expected, got %s and %s' % (tuple(x.shape), tuple(y.shape)))
+    if alpha != 2 or not _au_dense_ok(x):
+        return _au_alignment(x, y, alpha)
+    idx = torch.arange(x.shape[0], device=x.device)
+    return _au_fused(torch.cat([x, y], dim=0), x.shape[0], idx, idx, 0.0, 1.0, AU_ALIGN)[1]
+
+
+def uniformity(x):
+    """loss_utils.uniformity (loss_utils.py:82-86) for dense [B, d] rows on the device: the fused kernels with identity indices"""
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise ValueError('uniformity: a [B, d] tensor expected, got %s' % (tuple(x.shape),))
+    if not _au_dense_ok(x):
+        return _au_uniformity(x)
+    idx = torch.arange(x.shape[0], device=x.device)
+    return _au_fused(x, 0, idx, idx, 2.0, 1.0, AU_UNIFORM_POS)[2]          # gamma * (0 + uniformity(x)) / 2 with gamma = 2
+
+
+# ----------------------------------------------------------------------------------------------
 # the stacked parameter table [user_embeds; item_embeds] without the per-forward concatenation (reference lightgcn.py:34)
 # ----------------------------------------------------------------------------------------------
 def stacked_alias(u, i):

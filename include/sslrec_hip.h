@@ -443,6 +443,20 @@ int sslrec_bpr_bwd_kept_f32(const float *Ta, const int64_t *ia, const float *Tp,
                             const float *Tn, const int64_t *in, int32_t B, int32_t d, int32_t variant, float divisor,
                             const float *gscale_dev, float *dTa, float *dTp, float *dTn, void *ws, float *zero_table,
                             size_t zero_elems, void *stream);
+/* The backward STAGED BY THE FORWARD launch (a forward whose backward is known to follow): two launches per step instead of three.
+ *   fwd_staged : everything the forward does (loss_out[0], and loss_out[1] = loss_out[0] + add_in[0] when add_in != NULL; same
+ *        ws and the same bits), and for every triple the three gradient rows for an upstream gradient of exactly 1, staged in the KEPT
+ *        workspace bwd_ws (sslrec_bpr_bwd_ws_bytes, cleared by sslrec_bpr_bwd_table_init or left clean by the previous call) with
+ *        their destination rows of dTa / dTp / dTn registered; zero_table / zero_elems as in bwd_kept.  All three roles indexed,
+ *        3B <= 16384, d <= 256.  The rows are loaded once for the loss and the gradient.
+ *   bwd_from_staged : adds the staged rows, each multiplied by gscale_dev[0], into the registered destinations (deterministic, as
+ *        bwd) and leaves bwd_ws's table clean.  For gscale = 1 the result has the bits of bwd_kept.  Until this call (or a
+ *        sslrec_bpr_bwd_table_init) bwd_ws's table holds the staged keys: no other call may use it in between. */
+int sslrec_bpr_fwd_staged_f32(const float *Ta, const int64_t *ia, const float *Tp, const int64_t *ip,
+                              const float *Tn, const int64_t *in, int32_t B, int32_t d, int32_t variant, float divisor,
+                              const float *add_in, float *ws, float *loss_out, float *dTa, float *dTp, float *dTn,
+                              void *bwd_ws, float *zero_table, size_t zero_elems, void *stream);
+int sslrec_bpr_bwd_from_staged_f32(int32_t B, int32_t d, const float *gscale_dev, void *bwd_ws, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * InfoNCE against ALL rows of a view (replaces cal_infonce_loss,

@@ -65,8 +65,13 @@ __device__ __forceinline__ void det_insert(const DetTable &t, const float *row_p
 // on the same table needs no clearing launch.  The other contributors of a duplicated slot only ever read cnt / first to find out
 // that they are not the owner: before the clear they see cnt >= 2 and first = the owner, after it cnt = 0 and first = MAX -- either
 // way "not me".
-static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int K, const float *__restrict__ G, int d, int self_clean) {
+// UP: every contribution is multiplied by the device scalar up[0] as it is read (sslrec_bpr_bwd_from_staged_f32: rows staged for an
+// upstream gradient of 1; x * 1.0f is exact, so up[0] == 1 gives the bits of the unscaled form)
+template <bool UP>
+__device__ __forceinline__ void det_reduce_body(const DetTable &t, int K, const float *__restrict__ G, int d, int self_clean, const float *up) {
     const int lane = threadIdx.x & 63;
+    const float u = UP ? up[0] : 1.f;
+#define DET_G(i) (UP ? G[i] * u : G[i])
 #define DET_RELEASE_SLOT() if (self_clean && lane == 0) { t.key[slot] = 0ull; t.cnt[slot] = 0; t.first[slot] = 0x7fffffff; }
     for (int e = blockIdx.x * 4 + wave_in_block(); e < K; e += gridDim.x * 4) {
         const int slot = t.slot_of[e];
@@ -74,7 +79,7 @@ static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int 
         const int c = t.cnt[slot];
         float *row = reinterpret_cast<float *>((uintptr_t)t.key[slot]);
         if (c == 1) {
-            for (int k = lane; k < d; k += 64) row[k] += G[(size_t)e * d + k];
+            for (int k = lane; k < d; k += 64) row[k] += DET_G((size_t)e * d + k);
             DET_RELEASE_SLOT()
             continue;
         }
@@ -92,7 +97,7 @@ static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int 
                 float acc = 0.f;
 #pragma unroll
                 for (int i = 0; i < DET_LIST; ++i)
-                    if (i < c) acc += G[(size_t)ids[i] * d + k];
+                    if (i < c) acc += DET_G((size_t)ids[i] * d + k);
                 row[k] += acc;
             }
             DET_RELEASE_SLOT()
@@ -107,7 +112,7 @@ static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int 
                     const int id = j0 + b;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        if (lane + 64 * q < d) acc[q] += G[(size_t)id * d + lane + 64 * q];
+                        if (lane + 64 * q < d) acc[q] += DET_G((size_t)id * d + lane + 64 * q);
                 }
             }
 #pragma unroll
@@ -117,6 +122,16 @@ static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int 
         }
     }
 #undef DET_RELEASE_SLOT
+#undef DET_G
+}
+
+static __global__ __launch_bounds__(256) void det_reduce_kernel(DetTable t, int K, const float *__restrict__ G, int d, int self_clean) {
+    det_reduce_body<false>(t, K, G, d, self_clean, nullptr);
+}
+
+static __global__ __launch_bounds__(256) void det_reduce_scaled_kernel(DetTable t, int K, const float *__restrict__ G, int d, int self_clean,
+                                                                       const float *__restrict__ up) {
+    det_reduce_body<true>(t, K, G, d, self_clean, up);
 }
 
 
@@ -133,6 +148,14 @@ static inline int det_reduce(const DetTable &tab, int K, const float *G, int d, 
     int blocks = (K + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(det_reduce_kernel, dim3(blocks), dim3(256), 0, st, tab, K, G, d, self_clean);
+    SSLREC_LAUNCH_CHECK();
+    return 0;
+}
+
+static inline int det_reduce_scaled(const DetTable &tab, int K, const float *G, int d, const float *up, hipStream_t st, int self_clean) {
+    int blocks = (K + 3) / 4;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(det_reduce_scaled_kernel, dim3(blocks), dim3(256), 0, st, tab, K, G, d, self_clean, up);
     SSLREC_LAUNCH_CHECK();
     return 0;
 }

@@ -96,9 +96,11 @@ __device__ __forceinline__ void finish_by_last_block(float *ws, float block_part
     }
     __syncthreads();
     if (!is_last) return;
-    float v = 0.f;
-    for (int i = threadIdx.x; i < n_blocks; i += 256) v += __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s[threadIdx.x] = v;
+    if (threadIdx.x < 256) {      // (the first 256 threads add, whatever the workgroup's size: bpr_fwd_staged_kernel has 1024)
+        float v = 0.f;
+        for (int i = threadIdx.x; i < n_blocks; i += 256) v += __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s[threadIdx.x] = v;
+    }
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
@@ -183,6 +185,86 @@ __global__ __launch_bounds__(256) void bpr_bwd_stage_kernel(const float *Ta, con
             const int64_t *idx = lane == 0 ? ia : lane == 1 ? ip : in;
             float *dst = lane == 0 ? dTa + ra * d : lane == 1 ? dTp + rp * d : dTn + rn * d;
             if (idx) det_insert(tab, dst, 3 * b + lane); else tab.slot_of[3 * b + lane] = -1;
+        }
+    }
+}
+
+// bpr_fwd_kernel and bpr_bwd_stage_kernel (for an upstream gradient of exactly 1) in ONE launch: the three rows of a triple are loaded
+// once and serve the loss term, the coefficient and the three gradient rows; the gradient table is zeroed here as the stage kernel
+// does.  The LOSS keeps bpr_fwd_kernel's bits: the same 256 workgroups, and the term of triple b still belongs to wave slot
+// (b / 4) % 256, b % 4 -- but the workgroup has 16 waves, wave 4 j + w computes the terms it = j, j + 4 of slot w (one triple per wave
+// at B = 4096 instead of a chain of four) and thread 0 adds every slot's terms in ascending it like the forward kernel's lane 0 does.
+// The gradient rows keep bpr_bwd_stage_kernel's bits for gscale = 1 (1.0f / divisor is what gscale[0] / divisor gives there).
+// Order of work: rows -> terms -> loss published (finish_by_last_block) -> rows staged and keys inserted, so the integer atomics of
+// det_insert are not on the path of the loss.  3 B <= DET_MAX bounds a slot at STAGED_IT terms.
+#define STAGED_WAVES 16
+#define STAGED_IT 8      // terms per wave slot: 2 per wave
+static_assert(DET_MAX / 3 <= STAGED_IT * 4 * BPR_BLOCKS, "a slot of bpr_fwd_staged_kernel holds STAGED_IT terms");
+__global__ __launch_bounds__(64 * STAGED_WAVES) void bpr_fwd_staged_kernel(const float *Ta, const int64_t *ia, const float *Tp,
+                                                                           const int64_t *ip, const float *Tn, const int64_t *in,
+                                                                           int B, int d, int variant, float *ws, float divisor,
+                                                                           const float *add_in, float *out, int one_launch,
+                                                                           float *dTa, float *dTp, float *dTn, float *G, DetTable tab,
+                                                                           f32x4 *zero_tab, size_t zero_n4) {
+    __shared__ float term[STAGED_IT][4];
+    const int lane = threadIdx.x & 63;
+    const int v = wave_in_block(), w = v & 3, j = v >> 2;
+    for (size_t i = (size_t)blockIdx.x * (64 * STAGED_WAVES) + threadIdx.x; i < zero_n4; i += (size_t)gridDim.x * (64 * STAGED_WAVES))
+        zero_tab[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nw = gridDim.x * 4, slot = blockIdx.x * 4 + w;
+    float av[2][4], pv[2][4], nv[2][4], s[2];
+    int64_t ra[2], rp[2], rn[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int b = slot + (4 * r + j) * nw;      // (< 2^31: nw = 1024, B <= DET_MAX / 3)
+        if (b >= B) continue;                       // wave-uniform
+        ra[r] = ia[b]; rp[r] = ip[b]; rn[r] = in[b];
+        const float *a = Ta + ra[r] * d;
+        const float *p = Tp + rp[r] * d;
+        const float *n = Tn + rn[r] * d;
+        float dp = 0.f, dn = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = lane + 64 * q;
+            if (k < d) {
+                av[r][q] = a[k]; pv[r][q] = p[k]; nv[r][q] = n[k];
+                dp = fmaf(av[r][q], pv[r][q], dp);
+                dn = fmaf(av[r][q], nv[r][q], dn);
+            }
+        }
+        dp = wave_sum(dp);
+        dn = wave_sum(dn);
+        if (lane == 0) term[4 * r + j][w] = bpr_term(dn - dp, variant);
+        s[r] = (1.0f / divisor) * bpr_dterm(dn - dp, variant);
+    }
+    __syncthreads();
+    float partial = 0.f;
+    if (threadIdx.x == 0) {
+        float local[4];
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            local[ww] = 0.f;
+            for (int it = 0; it < STAGED_IT && blockIdx.x * 4 + ww + it * nw < B; ++it) local[ww] += term[it][ww];
+        }
+        partial = (local[0] + local[1]) + (local[2] + local[3]);
+    }
+    finish_by_last_block(ws, partial, gridDim.x, 1.f, divisor, add_in, out, one_launch);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int b = slot + (4 * r + j) * nw;
+        if (b >= B) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = lane + 64 * q;
+            if (k < d) {
+                G[(size_t)(3 * b + 0) * d + k] = s[r] * (nv[r][q] - pv[r][q]);
+                G[(size_t)(3 * b + 1) * d + k] = -s[r] * av[r][q];
+                G[(size_t)(3 * b + 2) * d + k] = s[r] * av[r][q];
+            }
+        }
+        if (lane < 3) {      // one lane per role
+            float *dst = lane == 0 ? dTa + ra[r] * d : lane == 1 ? dTp + rp[r] * d : dTn + rn[r] * d;
+            det_insert(tab, dst, 3 * b + lane);
         }
     }
 }
@@ -299,6 +381,35 @@ extern "C" int sslrec_bpr_bwd_kept_f32(const float *Ta, const int64_t *ia, const
                                        size_t zero_elems, void *stream) {
     if (!ws || 3 * (size_t)B > DET_MAX || d > 256) return SSLREC_E_BADARG;      // (this form exists for the table it keeps clean)
     return bpr_bwd_any(Ta, ia, Tp, ip, Tn, in, B, d, variant, divisor, gscale_dev, dTa, dTp, dTn, ws, stream, true, zero_table, zero_elems);
+}
+
+extern "C" int sslrec_bpr_fwd_staged_f32(const float *Ta, const int64_t *ia, const float *Tp, const int64_t *ip,
+                                         const float *Tn, const int64_t *in, int32_t B, int32_t d, int32_t variant, float divisor,
+                                         const float *add_in, float *ws, float *loss_out, float *dTa, float *dTp, float *dTn,
+                                         void *bwd_ws, float *zero_table, size_t zero_elems, void *stream) {
+    if (!Ta || !Tp || !Tn || !ia || !ip || !in || !ws || !loss_out || !dTa || !dTp || !dTn || !bwd_ws || B <= 0 || d <= 0 || d > 256 ||
+        3 * (size_t)B > DET_MAX || (variant != 0 && variant != 1) || !(divisor != 0.f))
+        return SSLREC_E_BADARG;
+    if (zero_table && ((zero_elems & 3) || ((uintptr_t)zero_table & 15))) return SSLREC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    float *G = (float *)bwd_ws;
+    const DetTable tab = det_table(G + (size_t)3 * B * d);
+    const int one = one_launch_reduce() ? 1 : 0;
+    hipLaunchKernelGGL(bpr_fwd_staged_kernel, dim3(BPR_BLOCKS), dim3(64 * STAGED_WAVES), 0, st, Ta, ia, Tp, ip, Tn, in, B, d, variant, ws,
+                       divisor, add_in, loss_out, one, dTa, dTp, dTn, G, tab, reinterpret_cast<f32x4 *>(zero_table),
+                       zero_table ? zero_elems / 4 : (size_t)0);
+    SSLREC_LAUNCH_CHECK();
+    if (!one) {
+        hipLaunchKernelGGL(finish_partials_kernel, dim3(1), dim3(256), 0, st, ws, BPR_BLOCKS, 1.f, divisor, add_in, loss_out);
+        SSLREC_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int sslrec_bpr_bwd_from_staged_f32(int32_t B, int32_t d, const float *gscale_dev, void *bwd_ws, void *stream) {
+    if (!gscale_dev || !bwd_ws || B <= 0 || d <= 0 || d > 256 || 3 * (size_t)B > DET_MAX) return SSLREC_E_BADARG;
+    float *G = (float *)bwd_ws;
+    return det_reduce_scaled(det_table(G + (size_t)3 * B * d), 3 * B, G, d, gscale_dev, (hipStream_t)stream, 1);
 }
 
 extern "C" int sslrec_scatter_add_rows_f32(const float *src, const int64_t *idx, int32_t B, int32_t d,

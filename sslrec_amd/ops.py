@@ -172,6 +172,9 @@ _KEPT_WS = collections.OrderedDict()      # (device, B, d) -> [workspace, stream
 _KEPT_WS_MAX = 8                          # (~1.7 MB + 12 B d bytes each -- variable batch sizes must not pile them up)
 _KEPT_WS_LOCK = threading.Lock()          # (two Python threads must not initialise / evict at once; a workspace still serves one stream at a time)
 SSLREC_KEPT_SCATTER = os.environ.get('SSLREC_KEPT_SCATTER', '1') != '0'      # 0: a fresh workspace + a clearing launch per BPR backward
+# SSLREC_BPR_STAGED=0: the stacked BPR's forward computes the loss only and its backward stages and reduces (three launches, the form
+# before); default: a forward that autograd will differentiate also stages the backward's rows (sslrec_bpr_fwd_staged_f32), two launches
+BPR_STAGED = os.environ.get('SSLREC_BPR_STAGED', '1') != '0'
 
 
 def _bpr_bwd_ws(device, B, d):
@@ -183,6 +186,19 @@ def _bpr_bwd_ws(device, B, d):
     n = lib.sslrec_bpr_bwd_ws_bytes(B, d) // 4 + 1
     if not SSLREC_KEPT_SCATTER or 3 * B > 16384 or d > 256 or B <= 0:
         return torch.empty(n, dtype=torch.float32, device=device), False
+    ws = _kept_ws(device, B, d)
+    st = ws._sslrec_stage
+    if st[1]:      # a forward staged its rows here and its backward has not run (and now cannot use them: the generation moves on)
+        _lib.check(lib.sslrec_bpr_bwd_table_init(ws.data_ptr(), int(B), int(d), _stream()), 'sslrec_bpr_bwd_table_init')
+        st[0], st[1] = st[0] + 1, False
+    return ws, True
+
+
+def _kept_ws(device, B, d):
+    """the kept workspace itself.  It carries `_sslrec_stage` = [generation, staged]: `staged` = its scatter table holds the keys of a
+    sslrec_bpr_fwd_staged_f32 that no backward has consumed yet, `generation` counts the stagings and their cancellations"""
+    lib = _lib.load()
+    n = lib.sslrec_bpr_bwd_ws_bytes(B, d) // 4 + 1
     dev = torch.device(device)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(B), int(d))
     cur = torch.cuda.current_stream(dev)
@@ -191,6 +207,7 @@ def _bpr_bwd_ws(device, B, d):
         if ent is None:
             ws = torch.empty(n, dtype=torch.float32, device=dev)
             _lib.check(lib.sslrec_bpr_bwd_table_init(ws.data_ptr(), int(B), int(d), _stream()), 'sslrec_bpr_bwd_table_init')
+            ws._sslrec_stage = [0, False]
             ent = _KEPT_WS[key] = [ws, cur]
             while len(_KEPT_WS) > _KEPT_WS_MAX and not torch.cuda.is_current_stream_capturing():
                 #  the dropped workspace was allocated on one stream and may last have been used on another (ent[1]): tell the
@@ -204,7 +221,7 @@ def _bpr_bwd_ws(device, B, d):
                 if not torch.cuda.is_current_stream_capturing():
                     cur.wait_stream(ent[1])
                 ent[1] = cur
-    return ent[0], True
+    return ent[0]
 
 
 def _check_kept(rc, what, device, B, d):
@@ -1287,7 +1304,7 @@ class _BprStackedFn(torch.autograd.Function):
     `bpr_loss + reg_loss`): outputs (total, bpr), the gradient of `total` flows to the table and, unchanged, to `add`."""
 
     @staticmethod
-    def forward(ctx, table, n_user, ancs, poss, negs, variant, divisor, add):
+    def forward(ctx, table, n_user, ancs, poss, negs, variant, divisor, add, stage):
         _need_gpu(table)
         table = _f32c(table)
         ia, ip, in_ = _idx(ancs), _idx(poss), _idx(negs)
@@ -1299,7 +1316,28 @@ class _BprStackedFn(torch.autograd.Function):
         ctx.save_for_backward(table, ia, ip, in_)
         ctx.meta = (B, d, variant, int(n_user), float(divisor))
         ctx.two = add is not None
+        ctx.staged = None
         ctx.set_materialize_grads(False)
+        if stage and SSLREC_KEPT_SCATTER and 0 < 3 * B <= 16384 and d <= 256 and table.numel() % 4 == 0:
+            # the backward is known to follow: this launch also stages its rows (for an upstream gradient of 1), registers their
+            # destinations in the kept workspace and zeroes the gradient table; the backward is then the reduction alone.  The
+            # workspace is shared per (device, B, d): the record's generation tells the backward whether the rows are still its own.
+            if add is not None:
+                _need_gpu(add)
+            addc = None if add is None else add.detach().reshape(1).to(torch.float32).contiguous()
+            out = torch.empty(1 if add is None else 2, dtype=torch.float32, device=table.device)
+            wsb, _ = _bpr_bwd_ws(table.device, B, d)      # (clears the table first if an earlier staging was never consumed)
+            grad = torch.empty_like(table)
+            q = grad.data_ptr()
+            qi = q + int(n_user) * d * 4
+            rc = lib.sslrec_bpr_fwd_staged_f32(p, ia.data_ptr(), pi, ip.data_ptr(), pi, in_.data_ptr(), B, d, variant, float(divisor),
+                                               _ptr(addc), ws.data_ptr(), out.data_ptr(), q, qi, qi, wsb.data_ptr(), q, grad.numel(),
+                                               _stream())
+            _check_kept(rc, 'sslrec_bpr_fwd_staged_f32', table.device, B, d)
+            st = wsb._sslrec_stage
+            st[0], st[1] = st[0] + 1, True
+            ctx.staged = (wsb, st[0], grad)
+            return out.reshape(()) if add is None else (out[1].reshape(()), out[0].reshape(()))
         if add is None:
             out = torch.empty(1, dtype=torch.float32, device=table.device)
             rc = lib.sslrec_bpr_fwd_f32(p, ia.data_ptr(), pi, ip.data_ptr(), pi, in_.data_ptr(), B, d, variant, float(divisor),
@@ -1325,9 +1363,19 @@ class _BprStackedFn(torch.autograd.Function):
         else:
             g, g_add = grads[0], None
         if g is None:
-            return None, None, None, None, None, None, None, g_add
+            return None, None, None, None, None, None, None, g_add, None
         g = g.reshape(1).to(torch.float32).contiguous()
         lib = _lib.load()
+        staged, ctx.staged = ctx.staged, None      # (a second backward under retain_graph takes the three-launch form below)
+        if staged is not None:
+            wsb, gen, grad = staged
+            if _kept_ws(table.device, B, d) is wsb and wsb._sslrec_stage == [gen, True]:      # nobody has used the workspace since
+                wsb._sslrec_stage[1] = False
+                rc = lib.sslrec_bpr_bwd_from_staged_f32(B, d, g.data_ptr(), wsb.data_ptr(), _stream())
+                _check_kept(rc, 'sslrec_bpr_bwd_from_staged_f32', table.device, B, d)
+                if SPARSE_GRAD:
+                    _tag_row_bits(grad, RowBits.from_indices(table.shape[0], ia, 0, ip, n_user, in_, n_user))
+                return grad, None, None, None, None, None, None, g_add, None
         ws, kept = _bpr_bwd_ws(table.device, B, d)
         fused_zero = kept and B > 0 and table.numel() % 4 == 0      # the staging launch zeroes the gradient table itself: no fill launch
         grad = torch.empty_like(table) if fused_zero else torch.zeros_like(table)
@@ -1341,14 +1389,17 @@ class _BprStackedFn(torch.autograd.Function):
         _check_kept(rc, 'sslrec_bpr_bwd_f32', table.device, B, d)
         if SPARSE_GRAD:      # rows ancs / n_user + poss / n_user + negs are the only ones written
             _tag_row_bits(grad, RowBits.from_indices(table.shape[0], ia, 0, ip, n_user, in_, n_user))
-        return grad, None, None, None, None, None, None, g_add
+        return grad, None, None, None, None, None, None, g_add, None
 
 
 def bpr_loss_stacked(table, n_user, ancs, poss, negs, variant=0, divisor=1.0, add=None):
     """Fused gather + BPR on the stacked [users; items] table the propagation produces (no slicing,
     one [N, d] gradient buffer): rows ancs / n_user + poss / n_user + negs (lightgcn.py:49-52).
     add (0-d tensor): returns (bpr + add, bpr) from the same launch."""
-    return _BprStackedFn.apply(table, int(n_user), ancs, poss, negs, int(variant), float(divisor), add)
+    # (grad mode is off inside Function.forward: whether a backward can follow is decided here.  A forward under no_grad, or on a table
+    # that takes no gradient, stages nothing and costs what it did)
+    stage = BPR_STAGED and torch.is_grad_enabled() and table.requires_grad
+    return _BprStackedFn.apply(table, int(n_user), ancs, poss, negs, int(variant), float(divisor), add, stage)
 
 
 def bpr_loss_gathered(user_table, item_table, ancs, poss, negs, variant=0, divisor=1.0):

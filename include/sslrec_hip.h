@@ -790,6 +790,64 @@ int sslrec_au_fwd_f32(const float *T, int32_t N, int32_t n_user, int32_t d, cons
 int sslrec_au_bwd_f32(int32_t N, int32_t n_user, int32_t d, const int64_t *ancs, const int64_t *poss, int32_t B, float scale, float gamma,
                       int32_t terms, const float *out, const float *g_align, const float *g_uniform, float *dT, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * VGAE edge decoder of AdaGCL over all entries of a pattern (csrc/edgemlp.hip), models/general_cf/adagcl.py:221-237 (vgae_generate):
+ *     edge_pred = self.sigmoid(self.decoder(x[edge_index[0]] * x[edge_index[1]]))       decoder = ReLU, Linear(d, d), ReLU, Linear(d, 1)
+ *     mask = ((edge_pred + 0.5).floor()).type(t.bool)
+ *     newVals = vals[mask];  newVals = newVals / (newVals.shape[0] / edgeNum[0]);  newIdxs = idxs[:, mask]
+ * The pattern is given as the per-entry arrays of a plan's CSR (sslrec_sddmm_f32): row_of_entry, col, perm [nnz].  X [n, d] fp32
+ * row-major serves both ends (the adjacency is square), W1 [d, d] row-major as nn.Linear stores it ([out, in]), b1 [d], w2 [d], b2 [1]
+ * (device memory: no host round trip for a parameter).  d in {32, 64, 128}.  Forward only.  Nothing of size nnz x d is written; the
+ * kept count is an integer sum: two runs give the same bits.  SSLREC_E_BADARG before any launch for a null pointer or a shape
+ * outside these ranges. */
+
+/* workgroups of the decoder launch at most = integers of its `counts` workspace */
+#define SSLREC_EDGE_MLP_SLOTS 1024
+
+/* logit[perm[k]] = w2 . relu(W1 relu(X[row] (.) X[col]) + b1) + b2 and keep[perm[k]] = logit >= 0 for every CSR position k.  The
+ * reference's floor(sigmoid(logit) + 0.5) differs from this flag only for fp32 logits within a few 2^-23 below 0, where the fp32
+ * sigmoid already rounds to 0.5.  counts [SSLREC_EDGE_MLP_SLOTS]: kept entries per workgroup, *n_counts (host) how many were written. */
+int sslrec_edge_mlp_fwd_f32(const int32_t *row_of_entry, const int32_t *col, const int32_t *perm, int32_t n_rows, int32_t n_cols, int32_t nnz,
+                            const float *X, int32_t d, const float *W1, const float *b1, const float *w2, const float *b2, float *logit,
+                            uint8_t *keep, int32_t *counts, int32_t *n_counts, void *stream);
+
+/* the same flags and counts from logits that something else computed (an embedding size without a decoder kernel) */
+int sslrec_edge_keep_flags(const float *logit, int32_t nnz, uint8_t *keep, int32_t *counts, int32_t *n_counts, void *stream);
+
+/* The finishing launch (:232-234): kept[0] = sum of the counts, out[e] = keep[e] ? vals[e] / (float)(kept / nnz) : 0 in entry order --
+ * the values of a re-valued view of the SAME plan, dropped entries 0.  kept == 0 writes zeros everywhere (no division by 0). */
+int sslrec_edge_keep_finish_f32(const float *vals, const uint8_t *keep, const int32_t *counts, int32_t n_counts, int32_t nnz, float *out,
+                                int32_t *kept, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * DenoiseNet's edge gate and symmetric normalisation of AdaGCL (csrc/gate.hip), models/general_cf/adagcl.py:274-338, :358-401, :340-347:
+ *     weight = self.get_attention(x[self.row], x[self.col], layer)              (Linear + ReLU per end, concat, Linear(2 d, 1))
+ *     gate_inputs = t.sigmoid((t.log(u) - t.log(1 - u) + log_alpha) / beta)     (training; t.sigmoid(log_alpha) otherwise)
+ *     mask = t.clamp(gate_inputs * (zeta - gamma) + gamma, 0.0, 1.0)
+ *     rowsum = t.sparse.sum(adj, dim=-1).to_dense() + 1e-6;  d_inv_sqrt = t.clamp(t.pow(rowsum, -0.5), 0.0, 10.0)
+ *     values = mask * d_inv_sqrt[row] * d_inv_sqrt[col]
+ *     l0_norm = t.mean(t.sigmoid(log_alpha - beta * t.log(-gamma / zeta)))
+ * with log_alpha[e] = p[row(e)] + q[col(e)] + bias[0]: the Linear + ReLU of the gathered rows is the gather of the transformed node
+ * table and the last Linear splits into two dots, so p, q [n] are node vectors.  The pattern is square (n x n), given as the plan's
+ * CSR (rowptr [n + 1], col, perm, row_of_entry [nnz]) and, for the backward, the transposed plan's (rowptr_t, col_t, perm_t);
+ * long_rows / long_rows_t: rows of more than SSLREC_EDGE_LONG_ROW entries (nullable when 0).  noise [nnz] in entry order = the
+ * logistic noise log u - log(1 - u), or null: then the gate's input is log_alpha itself (beta enters l0 only).  gamma < 0 < zeta,
+ * beta > 0, eps >= 0.  The ROW sums serve both ends, as in the reference.  No float atomics, every sum in a fixed order. */
+
+/* m [nnz] the clamped gates, s [n] = eps + their row sums, dinv [n], vals [nnz], l0 [1]; l0_row: n floats of workspace */
+int sslrec_edge_gate_fwd_f32(const int32_t *rowptr, const int32_t *col, const int32_t *perm, const int32_t *row_of_entry, int32_t n, int32_t nnz,
+                             const int32_t *long_rows, int32_t n_long, const float *p, const float *q, const float *bias, const float *noise,
+                             float gamma, float zeta, float beta, float eps, float *m, float *s, float *dinv, float *vals, float *l0,
+                             float *l0_row, void *stream);
+
+/* From dvals [nnz], dl0 [1] and the forward's m, s, dinv: dp, dq [n], dbias [1].  The gradient is 0 where the clamp at 10 or the
+ * [0, 1] clamp is active.  dla_ws: nnz floats, n_ws: 2 n floats of workspace, contents irrelevant on entry. */
+int sslrec_edge_gate_bwd_f32(const int32_t *rowptr, const int32_t *col, const int32_t *perm, const int32_t *long_rows, int32_t n_long,
+                             const int32_t *rowptr_t, const int32_t *col_t, const int32_t *perm_t, const int32_t *long_rows_t, int32_t n_long_t,
+                             int32_t n, int32_t nnz, const float *p, const float *q, const float *bias, const float *noise, float gamma,
+                             float zeta, float beta, float eps, const float *m, const float *s, const float *dinv, const float *dvals,
+                             const float *dl0, float *dp, float *dq, float *dbias, float *dla_ws, float *n_ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

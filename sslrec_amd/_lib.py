@@ -182,7 +182,15 @@ SIGNATURES = {
     'sslrec_au_ws_bytes': (C.c_size_t, [_I, _I]),
     'sslrec_au_fwd_f32': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _I, _P, _P, _P]),
     'sslrec_au_bwd_f32': (C.c_int, [_I, _I, _I, _P, _P, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P]),
+    'sslrec_edge_mlp_fwd_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    'sslrec_edge_keep_flags': (C.c_int, [_P, _I, _P, _P, C.POINTER(C.c_int32), _P]),
+    'sslrec_edge_keep_finish_f32': (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    'sslrec_edge_gate_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_edge_gate_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P]),
 }
+
+EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS
 
 _lib = None
 

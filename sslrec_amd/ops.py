@@ -6,9 +6,10 @@ CPU or eager-PyTorch fallback: tensors must live on a HIP device and the shared 
 must be built, otherwise these functions raise.
 """
 import ctypes as C
-
+import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -909,6 +910,189 @@ def edge_attention(pattern, q, k, v, head_num):
     if not edge_attention_fused_ok(d, head_num):
         return _edge_attention_composed(pattern, q, k, v, head_num)
     return _EdgeAttentionFn.apply(q, k, v, pattern, head_num)
+
+
+# ----------------------------------------------------------------------------------------------
+# AdaGCL's two view generators on [nnz] and [N] vectors: the VGAE edge decoder over all entries (adagcl.py:221-237, csrc/edgemlp.hip)
+# and DenoiseNet's edge gate with its symmetric normalisation (adagcl.py:274-338, :358-401, :340-347, csrc/gate.hip).  Nothing of
+# size nnz x d is stored; per-entry arrays are fp32 [nnz] in the caller's entry order.
+# ----------------------------------------------------------------------------------------------
+EDGE_MLP_DIMS = INTENT_DIMS
+EDGE_MLP_FUSED = os.environ.get('SSLREC_EDGE_MLP_FUSED', '1') != '0'      # 0: the composed torch expression at every size (measurement)
+EDGE_GATE_FUSED = os.environ.get('SSLREC_EDGE_GATE_FUSED', '1') != '0'
+
+
+def edge_mlp_fused_ok(d):
+    """whether csrc/edgemlp.hip has a decoder kernel for embedding size d; any other size runs the composed torch expression"""
+    return EDGE_MLP_FUSED and d in EDGE_MLP_DIMS
+
+
+def _edge_mlp_composed(csr, x, w1, b1, w2, b2):
+    """the reference's expression (adagcl.py:166, :224) with its [nnz, d] intermediates, in the caller's entry order"""
+    relu = torch.nn.functional.relu
+    rows, cols = csr['row_of_entry'].long(), csr['col'].long()
+    hidden = relu(torch.nn.functional.linear(relu(x[rows] * x[cols]), w1, b1))
+    out = torch.empty(rows.shape[0], dtype=torch.float32, device=x.device)
+    out[csr['perm'].long()] = hidden @ w2 + b2
+    return out
+
+
+def edge_mlp_logits(adj, x, w1, b1, w2, b2):
+    """logit[e] = w2 . relu(W1 relu(x[row(e)] (.) x[col(e)]) + b1) + b2 for every entry e of the square pattern of `adj` (a PropGraph, a
+    RevaluedView of one or a torch sparse adjacency): the VGAE decoder of AdaGCL before its sigmoid (adagcl.py:166, :224), fp32 [nnz] in
+    the caller's entry order.  x [N, d], w1 [d, d] and b1 [d] as nn.Linear holds them, w2 [d] or [1, d], b2 a one-element tensor.  Not
+    differentiable, like ops.sddmm (the reference calls it under no_grad).  d in {32, 64, 128} runs csrc/edgemlp.hip, which also leaves
+    the keep flags logit >= 0 and their per-workgroup counts on the returned tensor for edge_keep_view; the reference's
+    floor(sigmoid(logit) + 0.5) differs from that flag only for fp32 logits within a few 2^-23 below 0, where the fp32 sigmoid has
+    already rounded to 0.5.  Any other d runs the composed torch expression (edge_mlp_fused_ok)."""
+    _need_gpu(x, w1, b1, w2, b2)
+    graph = _pattern_graph(adj, 'edge_mlp_logits', x.device)
+    plan = graph.fwd
+    x, w1, b1, w2, b2 = (_f32c(t.detach()) for t in (x, w1, b1, w2.reshape(-1), b2.reshape(-1)))
+    d = x.shape[1] if x.dim() == 2 else -1
+    if x.dim() != 2 or plan.n_rows != plan.n_cols or x.shape[0] != plan.n_rows or tuple(w1.shape) != (d, d) or b1.numel() != d or \
+            w2.numel() != d or b2.numel() != 1:
+        raise ValueError('edge_mlp_logits: x %s, W1 %s, b1 [%d], w2 [%d], b2 [%d] for a %d x %d pattern' %
+                         (tuple(x.shape), tuple(w1.shape), b1.numel(), w2.numel(), b2.numel(), plan.n_rows, plan.n_cols))
+    csr = plan.device_csr()
+    if not edge_mlp_fused_ok(d):
+        return _edge_mlp_composed(csr, x, w1, b1, w2, b2)
+    logit = torch.empty(plan.nnz, dtype=torch.float32, device=x.device)
+    keep = torch.empty(plan.nnz, dtype=torch.uint8, device=x.device)
+    counts = torch.empty(_lib.EDGE_MLP_SLOTS, dtype=torch.int32, device=x.device)
+    n_counts = C.c_int32(0)
+    rc = _lib.load().sslrec_edge_mlp_fwd_f32(csr['row_of_entry'].data_ptr(), csr['col'].data_ptr(), csr['perm'].data_ptr(), plan.n_rows,
+                                             plan.n_cols, plan.nnz, x.data_ptr(), d, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                             logit.data_ptr(), keep.data_ptr(), counts.data_ptr(), C.byref(n_counts), _stream())
+    _lib.check(rc, 'sslrec_edge_mlp_fwd_f32')
+    logit._sslrec_keep = (keep, counts, int(n_counts.value))
+    return logit
+
+
+def edge_keep_view(adj, logits):
+    """(view, keep, kept) of vgae_generate (adagcl.py:229-237): keep [nnz] uint8 = logits >= 0, kept = their number (an int32 device
+    tensor of one element: no host round trip) and `view`, a RevaluedView of the cached plan of `adj` with the values
+    vals[e] * keep[e] / (kept / nnz) -- the dropped entries get the value 0, no new plan is built.  A view that keeps nothing has the
+    value 0 everywhere (the reference divides by 0); whoever reads `kept` on the host decides what that means."""
+    _need_gpu(logits)
+    graph = _pattern_graph(adj, 'edge_keep_view', logits.device)
+    nnz = graph.nnz
+    stash = getattr(logits, '_sslrec_keep', None)
+    logits_c = _entry_vec(logits.detach(), nnz, 'edge_keep_view')
+    lib = _lib.load()
+    if nnz == 0:
+        raise ValueError('edge_keep_view: the pattern has no entries')
+    if stash is not None and stash[0].numel() == nnz:
+        keep, counts, n_counts = stash
+    else:
+        keep = torch.empty(nnz, dtype=torch.uint8, device=logits.device)
+        counts = torch.empty(_lib.EDGE_MLP_SLOTS, dtype=torch.int32, device=logits.device)
+        n = C.c_int32(0)
+        _lib.check(lib.sslrec_edge_keep_flags(logits_c.data_ptr(), nnz, keep.data_ptr(), counts.data_ptr(), C.byref(n), _stream()),
+                   'sslrec_edge_keep_flags')
+        n_counts = int(n.value)
+    vals = getattr(graph, '_entry_vals', None)
+    if vals is None:                                             # the adjacency's own values in the caller's entry order, once per graph
+        fwd = graph.fwd
+        host = np.empty(nnz, dtype=np.float32)
+        host[fwd.perm_host] = fwd.csr_val_host
+        vals = graph._entry_vals = torch.from_numpy(host).to(graph.device)
+    out = torch.empty(nnz, dtype=torch.float32, device=logits.device)
+    kept = torch.empty(1, dtype=torch.int32, device=logits.device)
+    _lib.check(lib.sslrec_edge_keep_finish_f32(vals.data_ptr(), keep.data_ptr(), counts.data_ptr(), n_counts, nnz, out.data_ptr(),
+                                               kept.data_ptr(), _stream()), 'sslrec_edge_keep_finish_f32')
+    return RevaluedView(graph, out), keep, kept
+
+
+def _edge_gate_composed(csr, n, p, q, bias, gamma, zeta, beta, noise, eps):
+    """the reference's expression (adagcl.py:294-311, :328-334, :340-347) on the entry list, in the caller's entry order"""
+    rows, cols, perm = csr['row_of_entry'].long(), csr['col'].long(), csr['perm'].long()
+    la = p[rows] + q[cols] + bias
+    g = la if noise is None else (noise[perm] + la) / beta
+    m = torch.clamp(torch.sigmoid(g) * (zeta - gamma) + gamma, 0.0, 1.0)
+    s = torch.zeros(n, dtype=m.dtype, device=m.device).index_add(0, rows, m) + eps
+    dinv = torch.clamp(torch.pow(s, -0.5), 0.0, 10.0)
+    vals = torch.zeros_like(m).index_copy(0, perm, m * dinv[rows] * dinv[cols])
+    l0 = torch.sigmoid(la - beta * math.log(-gamma / zeta)).mean()
+    return vals, l0
+
+
+class _EdgeGateFn(torch.autograd.Function):
+    """saves p, q, bias, the noise, the gates m [nnz] and s, dinv [N]: [nnz] and [N] vectors only; the backward recomputes log_alpha"""
+
+    @staticmethod
+    def forward(ctx, p, q, bias, noise, graph, gamma, zeta, beta, eps):
+        p, q, bias = _f32c(p), _f32c(q), _f32c(bias)
+        fwd = graph.fwd
+        n, nnz = fwd.n_rows, fwd.nnz
+        csr = fwd.device_csr()
+        dev = p.device
+        m, vals = (torch.empty(nnz, dtype=torch.float32, device=dev) for _ in range(2))
+        s, dinv, l0_row = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        l0 = torch.empty((), dtype=torch.float32, device=dev)
+        lr, n_long = _long(csr)
+        rc = _lib.load().sslrec_edge_gate_fwd_f32(csr['rowptr'].data_ptr(), csr['col'].data_ptr(), csr['perm'].data_ptr(),
+                                                  csr['row_of_entry'].data_ptr(), n, nnz, lr, n_long, p.data_ptr(), q.data_ptr(), bias.data_ptr(),
+                                                  _ptr(noise) or None, gamma, zeta, beta, eps, m.data_ptr(), s.data_ptr(), dinv.data_ptr(),
+                                                  vals.data_ptr(), l0.data_ptr(), l0_row.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_edge_gate_fwd_f32')
+        ctx.graph, ctx.args, ctx.has_noise = graph, (gamma, zeta, beta, eps), noise is not None
+        ctx.save_for_backward(p, q, bias, m, s, dinv, *([noise] if noise is not None else []))
+        return vals, l0
+
+    @staticmethod
+    def backward(ctx, dvals, dl0):
+        saved = ctx.saved_tensors
+        p, q, bias, m, s, dinv = saved[:6]
+        noise = saved[6] if ctx.has_noise else None
+        graph = ctx.graph
+        gamma, zeta, beta, eps = ctx.args
+        fwd, bwd = graph.fwd, graph.bwd
+        n, nnz = fwd.n_rows, fwd.nnz
+        dev = p.device
+        dvals = torch.zeros(nnz, dtype=torch.float32, device=dev) if dvals is None else _entry_vec(dvals, nnz, 'edge_gate backward')
+        dl0 = torch.zeros((), dtype=torch.float32, device=dev) if dl0 is None else _f32c(dl0)
+        cf, cb = fwd.device_csr(), bwd.device_csr()
+        dp, dq = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+        dbias = torch.empty_like(bias)
+        dla = torch.empty(nnz, dtype=torch.float32, device=dev)
+        n_ws = torch.empty(2 * n, dtype=torch.float32, device=dev)
+        lr, n_long = _long(cf)
+        lr_t, n_long_t = _long(cb)
+        rc = _lib.load().sslrec_edge_gate_bwd_f32(cf['rowptr'].data_ptr(), cf['col'].data_ptr(), cf['perm'].data_ptr(), lr, n_long,
+                                                  cb['rowptr'].data_ptr(), cb['col'].data_ptr(), cb['perm'].data_ptr(), lr_t, n_long_t, n, nnz,
+                                                  p.data_ptr(), q.data_ptr(), bias.data_ptr(), _ptr(noise) or None, gamma, zeta, beta, eps,
+                                                  m.data_ptr(), s.data_ptr(), dinv.data_ptr(), dvals.data_ptr(), dl0.data_ptr(), dp.data_ptr(),
+                                                  dq.data_ptr(), dbias.data_ptr(), dla.data_ptr(), n_ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_edge_gate_bwd_f32')
+        return dp, dq, dbias, None, None, None, None, None, None
+
+
+def edge_gate(adj, p, q, bias, gamma, zeta, beta=1.0, noise=None, eps=0.0):
+    """(vals [nnz], l0) of DenoiseNet's hard-concrete edge gate and symmetric normalisation (adagcl.py:274-338, :358-401, :340-347) on the
+    square pattern of `adj` from the NODE vectors p, q [N] and the one-element `bias`: log_alpha[e] = p[row(e)] + q[col(e)] + bias,
+    m = clamp(sigmoid(g) * (zeta - gamma) + gamma, 0, 1) with g = (noise[e] + log_alpha[e]) / beta when the logistic noise
+    log u - log(1 - u) (fp32 [nnz], the caller's entry order) is given and g = log_alpha[e] otherwise, s[n] = eps + row sum of m,
+    dinv = clamp(s^-0.5, 0, 10) (a row whose gates are all 0 gives inf -> 10 at eps = 0), vals[e] = m[e] dinv[row] dinv[col] -- ROW sums
+    for both ends, as the reference has them -- and l0 = mean_e sigmoid(log_alpha[e] - beta log(-gamma / zeta)).  Differentiable in p, q
+    and bias; the autograd node saves [nnz] and [N] vectors only, has no float atomics and gives the same bits on every run."""
+    _need_gpu(p, q, bias, noise)
+    graph = _pattern_graph(adj, 'edge_gate', p.device)
+    if graph.bwd is None:
+        raise ValueError('edge_gate: the graph needs its transposed plan')
+    n_rows, n_cols = graph.shape
+    gamma, zeta, beta, eps = float(gamma), float(zeta), float(beta), float(eps)
+    if n_rows != n_cols or p.dim() != 1 or q.dim() != 1 or p.numel() != n_rows or q.numel() != n_rows or bias.numel() != 1:
+        raise ValueError('edge_gate: p %s, q %s, bias [%d] for a %d x %d pattern' % (tuple(p.shape), tuple(q.shape), bias.numel(), n_rows, n_cols))
+    if not (gamma < 0.0 < zeta and beta > 0.0 and eps >= 0.0):
+        raise ValueError('edge_gate: gamma < 0 < zeta, beta > 0 and eps >= 0 expected, got %r, %r, %r, %r' % (gamma, zeta, beta, eps))
+    if graph.nnz == 0 or n_rows == 0:
+        raise ValueError('edge_gate: the pattern has no entries')
+    if noise is not None:
+        noise = _entry_vec(noise.detach(), graph.nnz, 'edge_gate noise')
+    if not EDGE_GATE_FUSED:
+        return _edge_gate_composed(graph.fwd.device_csr(), n_rows, p.float(), q.float(), bias.float().reshape(()), gamma, zeta, beta, noise, eps)
+    return _EdgeGateFn.apply(p.float(), q.float(), bias.float().reshape(1), noise, graph, gamma, zeta, beta, eps)
 
 
 # ----------------------------------------------------------------------------------------------

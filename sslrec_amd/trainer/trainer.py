@@ -1,8 +1,8 @@
 """Training loop of the general-CF scenario; same public surface as the reference's `Trainer`
 (trainer/trainer.py:39-196): `create_optimizer`, `train_epoch`, `train` (optional early stop on
 the first configured metric), `evaluate`, `test`, `save_model`, `load_model`; per step
-zero_grad -> cal_loss -> backward -> step.  The eleven model-specific trainers upstream belong to
-models outside this path and are not provided."""
+zero_grad -> cal_loss -> backward -> step.  Of the eleven model-specific trainers upstream, AutoCF's and
+AdaGCL's are here (`AutoCFTrainer`, `AdaGCLTrainer`); the others belong to models outside this path."""
 import os
 import time
 from copy import deepcopy
@@ -390,4 +390,120 @@ class AutoCFTrainer(Trainer):
         self.step_losses = [sorted(parts) for _, parts in kept]          # names logged by every step of the last epoch
         steps = max(1, len(loader.dataset) // configs['train']['batch_size'])
         writer.add_scalar('Loss/train', ep_loss / steps, epoch_idx)
+        self.logger.log_loss(epoch_idx, loss_log, save_to_log=bool(configs['train']['log_loss']))
+
+
+class AdaGCLTrainer(Trainer):
+    """reference trainer/trainer.py:1114-1203: two view generators beside the model (`generator_1` a VGAE, `generator_2` a DenoiseNet),
+    three Adam optimizers, and a step of four phases in the reference's order -- the contrastive loss of the two generated views, the
+    information-bottleneck loss against that phase's outputs, the main BPR loss, then both generators' losses -- with the optimizer
+    steps and zero-grads where the reference has them (:1153-1186).  The gate temperature follows
+    max(0.05, init_temperature * temperature_decay^epoch) (:1157).  As in `_train_epoch_eager`, the step's 0-d tensors are read once
+    at the end of the epoch and summed on the host in the reference's order; a generated view that kept no entry is reported there.
+    train.hip_graph is refused: the step draws on the host (numpy's generator for the gate noise) and steps three optimizers between
+    its backward passes.  train.host_rng_replay is OFF for this trainer, as for AutoCFTrainer: VGAE's t.randn goes to the CPU
+    generator directly."""
+
+    def __init__(self, data_handler, logger):
+        from ..models.general_cf.adagcl import VGAE, DenoiseNet
+        super().__init__(data_handler, logger)
+        if configs['train'].get('hip_graph'):
+            raise NotImplementedError('train.hip_graph is not supported by AdaGCLTrainer: every step draws the gate noise on the host and '
+                                      'steps three optimizers between its backward passes')
+        self.generator_1 = VGAE().to(configs['device'])
+        self.generator_2 = DenoiseNet().to(configs['device'])
+
+    def create_optimizer(self, model):
+        self.generator_1.set_adagcl(model)
+        self.generator_2.set_adagcl(model)
+        model.set_denoiseNet(self.generator_2)
+        cfg = configs['optimizer']
+        if cfg['name'] != 'adam':
+            raise NotImplementedError("optimizer '%s'" % cfg['name'])
+        self.optimizer = optim.Adam(model.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'])
+        self.optimizer_gen_1 = optim.Adam(self.generator_1.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'])
+        self.optimizer_gen_2 = optim.Adam(filter(lambda p: p.requires_grad, self.generator_2.parameters()), lr=cfg['lr'],
+                                          weight_decay=cfg['weight_decay'])
+        self._graph = None
+
+    @log_exceptions
+    def train(self, model):
+        from .. import rng
+        if rng.active_host_replay(self._device_of(model)) is not None:
+            raise RuntimeError('AdaGCLTrainer draws from the CPU generators directly: disable the host generator replay '
+                               '(train.host_rng_replay) before training AdaGCL')
+        return self._train(model)
+
+    def generator_generate(self, generator):
+        with torch.no_grad():
+            return generator.vgae_generate(self.data_handler.torch_adj)
+
+    @staticmethod
+    def temperature(epoch_idx):
+        m = configs['model']
+        return max(0.05, m['init_temperature'] * pow(m['temperature_decay'], epoch_idx))
+
+    def train_step(self, model, batch_data, temperature, probe=None):
+        """one step (:1153-1188): (the four phase losses, the merged loss dictionary).  probe(name), if given, is called before the
+        optimizer steps that end the phases 'cl', 'ib' and 'main' (tests read the gradients there)."""
+        self.optimizer.zero_grad()
+        self.optimizer_gen_1.zero_grad()
+        self.optimizer_gen_2.zero_grad()
+        model._begin_step()
+        data1 = self.generator_generate(self.generator_1)
+
+        loss_cl, loss_dict_cl, out1, out2 = model.cal_loss_cl(batch_data, data1)
+        self._backward(loss_cl)
+        if probe is not None:
+            probe('cl')
+        self.optimizer.step()
+        self.optimizer.zero_grad()
+
+        loss_ib, loss_dict_ib = model.cal_loss_ib(batch_data, data1, out1, out2)
+        self._backward(loss_ib)
+        if probe is not None:
+            probe('ib')
+        self.optimizer.step()
+        self.optimizer.zero_grad()
+
+        loss_main, loss_dict_main = model.cal_loss(batch_data)
+        self._backward(loss_main)
+        loss_vgae, loss_dict_vgae = self.generator_1.cal_loss_vgae(self.data_handler.torch_adj, batch_data)
+        loss_denoise, loss_dict_denoise = self.generator_2.cal_loss_denoise(batch_data, temperature)
+        loss_generator = loss_vgae + loss_denoise
+        self._backward(loss_generator)
+        if probe is not None:
+            probe('main')
+        self.optimizer.step()
+        self.optimizer_gen_1.step()
+        self.optimizer_gen_2.step()
+        loss_dict = {**loss_dict_cl, **loss_dict_ib, **loss_dict_main, **loss_dict_vgae, **loss_dict_denoise}
+        return (loss_cl, loss_ib, loss_main, loss_generator), loss_dict
+
+    def train_epoch(self, model, epoch_idx):
+        from ..models.general_cf.adagcl import check_kept
+        loader = self.data_handler.train_dataloader
+        loader.dataset.sample_negs()
+        n_batches = len(loader)
+        model.train()
+        temperature = self.temperature(epoch_idx)
+        kept, names, views = [], None, []
+        for tem in loader:
+            batch_data = [x.long().to(configs['device']) for x in tem]
+            losses, loss_dict = self.train_step(model, batch_data, temperature)
+            if names is None:
+                names = list(loss_dict)
+            views.append(self.generator_1.last['kept'])
+            kept.append([x.detach().reshape(()).float() for x in losses] + [loss_dict[k].detach().reshape(()).float() for k in names])
+        loss_log, ep_loss = {}, 0.0
+        if kept:
+            check_kept(torch.cat(views))                                                          # the epoch's one synchronisation ...
+            host = torch.stack([torch.stack(row) for row in kept]).double().cpu().tolist()      # ... and its one transfer
+            for row in host:
+                ep_loss += sum(row[:4])
+                for name, value in zip(names, row[4:]):
+                    loss_log[name] = loss_log.get(name, 0.0) + value / n_batches
+        steps = max(1, len(loader.dataset) // configs['train']['batch_size'])
+        writer.add_scalar('Loss/train', ep_loss / steps, epoch_idx)
+        self.loss_log = loss_log
         self.logger.log_loss(epoch_idx, loss_log, save_to_log=bool(configs['train']['log_loss']))

@@ -227,6 +227,36 @@ int sslrec_spmm_swept_f32(const sslrec_swept_t *A, const int32_t *pack_override,
                           const int32_t *w_steps_override, const float *X, int32_t d, float *Y,
                           const sslrec_epilogue_t *epi, void *stream);
 
+/* sslrec_spmm_swept_f32 with one of two by-products of a training step compiled into the flush (the LightGCN step, lightgcn.py:38-56:
+ * forward products, reg_weight * |E0|^2, backward products with the regularizer's gradient).  Same arguments, and the same bits in
+ * Y / acc_out as sslrec_spmm_swept_f32 with the same epilogue; `step->flags` is exactly one of
+ *   SSLREC_STEP_SUMSQ       the launch ALSO writes sumsq_out[0] = sumsq_weight * sum of the squares of the n_rows * d elements of
+ *                           epi->acc_in.  Every output row is flushed exactly once and its acc_in row is in registers there, so the
+ *                           sum costs 4 FMAs per lane and row and the launch and table read of sslrec_sumsq_fwd_f32 go away.
+ *                           Deterministic: lanes, waves, workgroups and the launch are each added in a fixed order (the workgroup that
+ *                           finishes last adds the workgroups' partials: the scheme of sslrec_sumsq_fwd_f32), so two launches on one
+ *                           layout give the same bits; the order is not sslrec_sumsq_fwd_f32's, so the two may differ by rounding.
+ *                           Needs a plain valued launch: none of epi->axpy_x, x_row_bits, SSLREC_SCALE_PATTERN.
+ *                           sumsq_ws: sslrec_sumsq_ws_bytes() bytes, zero at entry (once: every launch leaves its ticket counters
+ *                           zero again); it may be the workspace of sslrec_sumsq_fwd_f32 as long as the launches are ordered.
+ *   SSLREC_STEP_AXPY_BATCH  needs epi->axpy_x.  The axpy_x rows are requested beside the acc_in rows, four flush passes at a time,
+ *                           instead of one dependent load per output row; valued and pattern launches.  The sumsq_* fields are unused.
+ * Both need: sslrec_swept_step_ok(A) == 1 (the one-workgroup-per-CU build, A->d in 32 .. 256), d == A->d (no embedding-column passes),
+ * epi->acc_in / acc_out and epi->n_sum_in == 0 -- otherwise SSLREC_E_BADARG and nothing is launched: the caller asks the predicate
+ * first and keeps sslrec_spmm_swept_f32 (and sslrec_sumsq_fwd_f32) everywhere else. */
+#define SSLREC_STEP_SUMSQ 1
+#define SSLREC_STEP_AXPY_BATCH 2
+typedef struct {
+    float *sumsq_ws;
+    float *sumsq_out;
+    float sumsq_weight;
+    int32_t flags;
+} sslrec_swept_step_t;
+int sslrec_swept_step_ok(const sslrec_swept_t *A);              /* 1: launches on A can take sslrec_spmm_swept_step_f32 */
+int sslrec_spmm_swept_step_f32(const sslrec_swept_t *A, const int32_t *pack_override, const float *val_override,
+                               const int32_t *w_steps_override, const float *X, int32_t d, float *Y,
+                               const sslrec_epilogue_t *epi, const sslrec_swept_step_t *step, void *stream);
+
 /* One product, several epilogues: SimGCL's three views (simgcl.py:29-31: two perturbed forwards + a clean one)
  * start from the SAME A.E0, so their first layer is one launch whose flush applies up to SSLREC_MAX_VIEWS
  * (noise, acc_in, acc_out, Y) sets; noise[k] NULL = clean view.  (The mirror image holds for the gradient of that

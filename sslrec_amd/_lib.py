@@ -83,6 +83,14 @@ class EpilogueStruct(C.Structure):
                 ('row_scale', C.c_void_p), ('scale_flags', C.c_int32)]
 
 
+STEP_SUMSQ, STEP_AXPY_BATCH = 1, 2      # SSLREC_STEP_*
+
+
+class SweptStepStruct(C.Structure):
+    """mirror of sslrec_swept_step_t"""
+    _fields_ = [('sumsq_ws', C.c_void_p), ('sumsq_out', C.c_void_p), ('sumsq_weight', C.c_float), ('flags', C.c_int32)]
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _F = C.c_float
@@ -101,6 +109,9 @@ SIGNATURES = {
     'sslrec_spmm_bundled_f32': (C.c_int, [C.POINTER(BundledStruct), _P, _P, _I, _P, C.POINTER(EpilogueStruct), _P, _P]),
     'sslrec_spmm_swept_f32': (C.c_int, [C.POINTER(SweptStruct), _P, _P, _P, _P, _I, _P, C.POINTER(EpilogueStruct), _P]),
     'sslrec_swept_deferred_sum_ok': (C.c_int, [C.POINTER(SweptStruct)]),
+    'sslrec_swept_step_ok': (C.c_int, [C.POINTER(SweptStruct)]),
+    'sslrec_spmm_swept_step_f32': (C.c_int, [C.POINTER(SweptStruct), _P, _P, _P, _P, _I, _P, C.POINTER(EpilogueStruct),
+                                             C.POINTER(SweptStepStruct), _P]),
     'sslrec_spmm_swept_views_f32': (C.c_int, [C.POINTER(SweptStruct), _P, _I, C.POINTER(EpilogueViewsStruct), _P]),
     'sslrec_swept_compact': (C.c_int, [C.POINTER(SweptStruct), _P, _P, _F, _P, _P, _P, _P]),
     'sslrec_edge_drop_compact': (C.c_int, [C.POINTER(CsrStruct), _P, _P, _F, _P, _P, _P, _P, _P]),

@@ -25,6 +25,7 @@
 // broadcast with a DPP row_newbcast.  A packed word is column | slot << 20 (-1 = pad).  The flush adds the chunks of a row
 // in slot order, applies the epilogue and writes each output row once.
 #include "common.h"
+#include "fin_reduce.h"
 #include "philox.h"
 #include "swept_fmt.h"
 #include <stdlib.h>
@@ -73,6 +74,9 @@ struct SweptArgs {
     int32_t scale_flags;
     int32_t acc_init;              // experiment switch (SSLREC_SWEPT_ACC_INIT=1): launches that write only acc_out start their one-slot rows' accumulators
                                    // from acc_in instead of zero (the read moves from the flush to the start of the kernel)
+    // SW_TAG_SSQ launches (sslrec_spmm_swept_step_f32): out[0] = weight * sum(acc_in^2) as a by-product of the flush's reads of acc_in
+    float *ssq_ws, *ssq_out;
+    float ssq_weight;
 };
 #define SWEPT_TRACE_MAXB 32
 
@@ -88,7 +92,16 @@ __device__ __forceinline__ void sw_store_sc1(sw_f32x4 *p, sw_f32x4 v) {
 // WPE = waves per SIMD the kernel is compiled for: 4 (one 1024-thread workgroup per CU, 128 VGPRs) or 8 (the half-size
 // layout of small matrices: two workgroups per CU, 64 VGPRs)
 // PAT = pattern product (SSLREC_SCALE_PATTERN): every entry has the weight 1, the value stream is not read
-template <int D, bool PASSES, int WPE, bool PAT>
+// TAG = by-products of the flush, compiled in per instantiation (the untagged builds carry neither their registers nor their code):
+// SW_TAG_SSQ (PASSES = false, WPE = 4, PAT = false, one view, no deferred sum): the sum of squares of the acc_in table.  Every output row
+// is flushed exactly once and its acc_in row passes through registers there, so a lane adds the squares of the components it reads
+// (4 FMAs per row) and the workgroups' partial sums are added in a fixed order by the one that finishes last (fin_reduce.h)
+// SW_TAG_AXB (PASSES = false, WPE = 4, either PAT, one view, no deferred sum, axpy_x given): the axpy_x rows of the prefetched passes and
+// of the first chunked pass are requested beside their acc_in rows, CH passes at a time, instead of one dependent load per flush_row
+#define SW_TAG_NONE 0
+#define SW_TAG_SSQ 1
+#define SW_TAG_AXB 2
+template <int D, bool PASSES, int WPE, bool PAT, int TAG = SW_TAG_NONE>
 __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
     extern __shared__ float4 acc[];
     constexpr int G = 256 / D;        // output rows per wave instruction
@@ -356,8 +369,13 @@ __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
     // the accumulator input of the row (prefetched), else it is read here
     // rsc = row_scale[row] (1 without it): a pattern launch's row sum times r[row] is the product's row; SSLREC_SCALE_Y / _ACC write
     // Y / acc_out times r[row] (the operand of the NEXT pattern launch: sslrec_epilogue_t.scale_flags); x * 1.f is exact
+    float ssq = 0.f;      // SW_TAG_SSQ: this lane's sum of squares of the acc_in components it has read
+    // SW_TAG_AXB: a call tagged AccAxGiven finds its axpy_x row in ax_row (requested by the caller beside acc_row) instead of reading it
+    typedef std::integral_constant<int, 1> AccAxGiven;      // (value converts to have_acc = true)
+    float4 ax_row = zero4;
     auto flush_row = [&](const int row, const int s0, const int n, auto have_acc_tag, const float4 acc_row, const float rsc) {
         constexpr bool have_acc = decltype(have_acc_tag)::value;
+        constexpr bool have_ax = std::is_same<decltype(have_acc_tag), AccAxGiven>::value;
         const bool live = row >= 0;
         float4 t = zero4;
         size_t at = 0;
@@ -415,8 +433,16 @@ __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
                     if constexpr (WPE == 4)      // (the 64-register build of the half-size layout does not take deferred sums: launch_swept_one)
                         if (a.n_sum_in) sa = sum_in_rows(sa, at);
                 }
+                if constexpr (TAG == SW_TAG_SSQ) {      // (live rows only: a dead record or lane never gets here)
+                    ssq = fmaf(sa.x, sa.x, ssq); ssq = fmaf(sa.y, sa.y, ssq); ssq = fmaf(sa.z, sa.z, ssq); ssq = fmaf(sa.w, sa.w, ssq);
+                }
                 sa.x += tk.x; sa.y += tk.y; sa.z += tk.z; sa.w += tk.w;
-                if (a.axpy_x) {                      // + alpha * x row (the regularizer's gradient in the last backward product)
+                if constexpr (TAG == SW_TAG_AXB) {   // (the launcher gives this build only launches with axpy_x: same arithmetic, same order)
+                    const float al = a.axpy_alpha * (a.axpy_scale ? *a.axpy_scale : 1.f);
+                    float4 xr = ax_row;
+                    if constexpr (!have_ax) xr = reinterpret_cast<const float4 *>(a.axpy_x)[at];
+                    sa.x = fmaf(al, xr.x, sa.x); sa.y = fmaf(al, xr.y, sa.y); sa.z = fmaf(al, xr.z, sa.z); sa.w = fmaf(al, xr.w, sa.w);
+                } else if (a.axpy_x) {               // + alpha * x row (the regularizer's gradient in the last backward product)
                     const float al = a.axpy_alpha * (a.axpy_scale ? *a.axpy_scale : 1.f);
                     const float4 xr = reinterpret_cast<const float4 *>(a.axpy_x)[at];
                     sa.x = fmaf(al, xr.x, sa.x); sa.y = fmaf(al, xr.y, sa.y); sa.z = fmaf(al, xr.z, sa.z); sa.w = fmaf(al, xr.w, sa.w);
@@ -446,7 +472,34 @@ __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
 #pragma unroll
         for (int u = 0; u < PFW; ++u) rscp[u] = rsv[frp[u] == -1 ? 0 : (frp[u] & 0xFFFFF)];
     }
-    if (pre_acc && a.n_sum_in == 0) {
+    if (TAG == SW_TAG_AXB && pre_acc && a.n_sum_in == 0) {
+        // acc_in and axpy_x rows of CH passes requested together (2 CH float4 live, as the deferred sum below keeps 12), then flushed
+        constexpr int CH = 4;
+#pragma unroll
+        for (int u0 = 0; u0 < PFW; u0 += CH) {
+            float4 base[CH], xr[CH];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const int uc = (u0 + c < PFW) ? u0 + c : 0;
+                const int row = (u0 + c < PFW) ? SW_FR_ROW(uc) : -1;
+                const size_t at = (size_t)(row >= 0 ? row : 0) * RS + CO + rs;
+                base[c] = zero4;
+                xr[c] = zero4;
+                if (row >= 0) {
+                    base[c] = reinterpret_cast<const float4 *>(a.acc_in[0])[at];
+                    xr[c] = reinterpret_cast<const float4 *>(a.axpy_x)[at];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const int uc = (u0 + c < PFW) ? u0 + c : 0;
+                if (u0 + c < PFW && u0 + c < wpasses) {      // uniform condition
+                    ax_row = xr[c];
+                    flush_row(SW_FR_ROW(uc), SW_FR_S0(uc), 1, AccAxGiven(), base[c], rscp[uc]);
+                }
+            }
+        }
+    } else if (pre_acc && a.n_sum_in == 0) {
         float4 accp[PFA];
 #pragma unroll
         for (int u = 0; u < PFW; ++u) {
@@ -519,12 +572,14 @@ __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
             const size_t at = (size_t)crow * RS + CO + rs;
             cacc = reinterpret_cast<const float4 *>(a.acc_in[0])[at];
             if (a.n_sum_in) cacc = sum_in_rows(cacc, at);
+            if constexpr (TAG == SW_TAG_AXB) ax_row = reinterpret_cast<const float4 *>(a.axpy_x)[at];
         }
     }
     if (!a.late_flush) SW_LDS_BARRIER();
     SW_TRACE_AT(SWEPT_TRACE_MAXB - 2)          // the workgroup's chunk flush starts
     if (cpasses > 0) {
-        if (WPE == 4 && pre_acc) flush_row(crow, cs0, cn, AccGiven(), cacc, crsc);
+        if (TAG == SW_TAG_AXB && WPE == 4 && pre_acc) flush_row(crow, cs0, cn, AccAxGiven(), cacc, crsc);
+        else if (WPE == 4 && pre_acc) flush_row(crow, cs0, cn, AccGiven(), cacc, crsc);
         else flush_row(crow, cs0, cn, AccRead(), zero4, crsc);
     }
     for (int it = 1; it < cpasses; ++it) {
@@ -534,6 +589,22 @@ __global__ __launch_bounds__(1024, WPE) void spmm_swept_kernel(SweptArgs a) {
         flush_row(row_i, live ? a.fstart[i] : 0, live ? a.fn[i] : 0, AccRead(), zero4, (rsv && row_i >= 0) ? rsv[row_i] : 1.f);
     }
     SW_TRACE_AT(SWEPT_TRACE_MAXB - 1)          // this wave's share of the flush is issued
+    if constexpr (TAG == SW_TAG_SSQ) {
+        // lanes -> wave (shuffles) -> workgroup (the 16 wave sums added in wave order) -> launch (fin_reduce.h).  No static LDS: the
+        // accumulators take all of it on some layouts, and they are dead once every wave has read its rows' chunks -- one more LDS
+        // barrier, then their first 1.3 KB serve as scratch: floats [0, 16) the wave sums, [32] the last-block flag, [64, 320) the tree
+        float *sm = reinterpret_cast<float *>(acc);
+        ssq = wave_sum(ssq);
+        SW_LDS_BARRIER();
+        if (lane == 0) sm[wave_in_block()] = ssq;
+        SW_LDS_BARRIER();
+        float part = 0.f;
+        if (tid == 0) {
+#pragma unroll
+            for (int w = 0; w < SWEPT_WAVES; ++w) part += sm[w];
+        }
+        finish_by_last_block_lds(a.ssq_ws, part, gridDim.x, a.ssq_weight, 1.f, nullptr, a.ssq_out, sm + 64, reinterpret_cast<int *>(sm + 32));
+    }
     stamp_end<true>(a.stamp);
 }
 
@@ -578,14 +649,14 @@ unsigned long long *sslrec_take_stamp() {
     return r;
 }
 
-template <int D, bool PASSES, int WPE, bool PAT>
+template <int D, bool PASSES, int WPE, bool PAT, int TAG = SW_TAG_NONE>
 static int launch_swept_pat(const SweptArgs &a, int n_blocks, hipStream_t st) {
     const size_t lds = (size_t)a.n_slots * D * 4;
     static bool attr_set[64] = {};      // per instantiation and per device: the attribute belongs to the device's code object
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SSLREC_E_BADARG;
     if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void *)spmm_swept_kernel<D, PASSES, WPE, PAT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipError_t e = hipFuncSetAttribute((const void *)spmm_swept_kernel<D, PASSES, WPE, PAT, TAG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            SSLREC_SWEPT_LDS_BYTES);
         if (e != hipSuccess) return (int)e;
         attr_set[dev] = true;
@@ -603,7 +674,7 @@ static int launch_swept_pat(const SweptArgs &a, int n_blocks, hipStream_t st) {
     b.acc_init = ainit;
     if (g_swept_trace && (size_t)n_blocks * SWEPT_WAVES * SWEPT_TRACE_MAXB <= g_swept_trace_stride)
         b.trace = g_swept_trace + (size_t)(g_swept_trace_launch++ % SWEPT_TRACE_RING) * g_swept_trace_stride;
-    hipLaunchKernelGGL((spmm_swept_kernel<D, PASSES, WPE, PAT>), dim3(n_blocks), dim3(1024), lds, st, b);
+    hipLaunchKernelGGL((spmm_swept_kernel<D, PASSES, WPE, PAT, TAG>), dim3(n_blocks), dim3(1024), lds, st, b);
     SSLREC_LAUNCH_CHECK();
     return 0;
 }
@@ -834,13 +905,13 @@ extern "C" int sslrec_swept_deferred_sum_ok(const sslrec_swept_t *A) {
     return !(A->n_blocks > 256 || (size_t)A->n_slots * A->d * 4 <= SSLREC_SWEPT_LDS_BYTES / 2);
 }
 
-extern "C" int sslrec_spmm_swept_f32(const sslrec_swept_t *A, const int32_t *pack_override, const float *val_override,
-                                     const int32_t *w_steps_override, const float *X, int32_t d, float *Y,
-                                     const sslrec_epilogue_t *epi, void *stream) {
+// the arguments of a one-view launch from the entry point's (0, or SSLREC_E_BADARG)
+static int swept_one_view_args(SweptArgs &a, const sslrec_swept_t *A, const int32_t *pack_override, const float *val_override,
+                               const int32_t *w_steps_override, const float *X, int32_t d, float *Y, const sslrec_epilogue_t *epi) {
     if (!swept_ok(A, X, d)) return SSLREC_E_BADARG;
     if (!Y && !(epi && epi->acc_out)) return SSLREC_E_BADARG;
     if (epi && epi->acc_out && !epi->acc_in) return SSLREC_E_BADARG;
-    SweptArgs a = {};
+    a = SweptArgs{};
     a.pack = pack_override ? pack_override : A->pack;
     a.val = val_override ? val_override : A->val;
     a.w_start = A->w_start;
@@ -881,7 +952,59 @@ extern "C" int sslrec_spmm_swept_f32(const sslrec_swept_t *A, const int32_t *pac
             a.sum_in[j] = epi->sum_in[j];
         }
     }
+    return 0;
+}
+
+extern "C" int sslrec_spmm_swept_f32(const sslrec_swept_t *A, const int32_t *pack_override, const float *val_override,
+                                     const int32_t *w_steps_override, const float *X, int32_t d, float *Y,
+                                     const sslrec_epilogue_t *epi, void *stream) {
+    SweptArgs a;
+    const int rc = swept_one_view_args(a, A, pack_override, val_override, w_steps_override, X, d, Y, epi);
+    if (rc != 0) return rc;
     return swept_dispatch(a, A, d, (hipStream_t)stream);
+}
+
+// can launches on this layout take sslrec_spmm_swept_step_f32?  The one-workgroup-per-CU build (its flush records and first chunked
+// pass ride through the sweep in registers) at the widths whose metadata blocks hold 8 or 16 steps
+extern "C" int sslrec_swept_step_ok(const sslrec_swept_t *A) {
+#ifdef SSLREC_SWEPT_ACC_INIT      // (that experiment build moves the read of acc_in out of the flush)
+    return 0;
+#else
+    if (!sslrec_swept_deferred_sum_ok(A)) return 0;
+    if ((size_t)A->n_slots * A->d * 4 > SSLREC_SWEPT_LDS_BYTES || A->n_cols > (1 << 20) || A->n_slots > 4095) return 0;
+    return A->d == 32 || A->d == 64 || A->d == 128 || A->d == 256;
+#endif
+}
+
+template <int TAG, bool PAT>
+static int launch_swept_tagged(const SweptArgs &a, const sslrec_swept_t *A, hipStream_t st) {
+    switch (A->d) {
+        case 32: return launch_swept_pat<32, false, 4, PAT, TAG>(a, A->n_blocks, st);
+        case 64: return launch_swept_pat<64, false, 4, PAT, TAG>(a, A->n_blocks, st);
+        case 128: return launch_swept_pat<128, false, 4, PAT, TAG>(a, A->n_blocks, st);
+        case 256: return launch_swept_pat<256, false, 4, PAT, TAG>(a, A->n_blocks, st);
+        default: return SSLREC_E_BADARG;
+    }
+}
+
+extern "C" int sslrec_spmm_swept_step_f32(const sslrec_swept_t *A, const int32_t *pack_override, const float *val_override,
+                                          const int32_t *w_steps_override, const float *X, int32_t d, float *Y,
+                                          const sslrec_epilogue_t *epi, const sslrec_swept_step_t *step, void *stream) {
+    if (!step || (step->flags != SSLREC_STEP_SUMSQ && step->flags != SSLREC_STEP_AXPY_BATCH)) return SSLREC_E_BADARG;
+    SweptArgs a;
+    const int rc = swept_one_view_args(a, A, pack_override, val_override, w_steps_override, X, d, Y, epi);
+    if (rc != 0) return rc;
+    // the tagged builds: one launch (no column passes) of the one-workgroup-per-CU kernel with an accumulator and no deferred sum
+    if (!sslrec_swept_step_ok(A) || d != A->d || !a.acc_out[0] || a.n_sum_in != 0) return SSLREC_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (step->flags == SSLREC_STEP_SUMSQ) {      // the plain valued product: everything else keeps sslrec_sumsq_fwd_f32
+        if (!step->sumsq_ws || !step->sumsq_out || a.axpy_x || a.x_bits || (a.scale_flags & SSLREC_SCALE_PATTERN)) return SSLREC_E_BADARG;
+        a.ssq_ws = step->sumsq_ws; a.ssq_out = step->sumsq_out; a.ssq_weight = step->sumsq_weight;
+        return launch_swept_tagged<SW_TAG_SSQ, false>(a, A, st);
+    }
+    if (!a.axpy_x) return SSLREC_E_BADARG;
+    if (a.scale_flags & SSLREC_SCALE_PATTERN) return launch_swept_tagged<SW_TAG_AXB, true>(a, A, st);
+    return launch_swept_tagged<SW_TAG_AXB, false>(a, A, st);
 }
 
 extern "C" int sslrec_spmm_swept_views_f32(const sslrec_swept_t *A, const float *X, int32_t d,

@@ -176,6 +176,16 @@ SSLREC_KEPT_SCATTER = os.environ.get('SSLREC_KEPT_SCATTER', '1') != '0'      # 0
 # SSLREC_BPR_STAGED=0: the stacked BPR's forward computes the loss only and its backward stages and reduces (three launches, the form
 # before); default: a forward that autograd will differentiate also stages the backward's rows (sslrec_bpr_fwd_staged_f32), two launches
 BPR_STAGED = os.environ.get('SSLREC_BPR_STAGED', '1') != '0'
+# SSLREC_REG_IN_FLUSH=0: propagate_sum's regularizer is always a launch of its own (sslrec_sumsq_fwd_f32); default: where the first
+# forward product can carry it (sslrec_swept_sumsq_ok), its flush forms the sum from the E0 rows it reads anyway
+REG_IN_FLUSH = os.environ.get('SSLREC_REG_IN_FLUSH', '1') != '0'
+REG_ROUTES = {'flush': 0, 'kernel': 0}      # how often propagate_sum's regularizer took which route (tests, diagnostics)
+# SSLREC_AXPY_BATCH=1 (opt-in): where the layout takes it (sslrec_swept_step_ok), a launch with an `axpy` operand requests its rows in
+# batches beside the accumulator rows instead of one by one inside the flush (same bits).  Measured (EXPERIMENTS.md F.2): 0-1 us of
+# the step eager, inside the spread of the other figures -- the launch pays for the 37 MB it reads, not for the round trips -- so the
+# default stays the plain form.
+AXPY_BATCH = os.environ.get('SSLREC_AXPY_BATCH', '0') == '1'
+AXPY_ROUTES = {'batched': 0, 'plain': 0}
 
 
 def _bpr_bwd_ws(device, B, d):
@@ -264,7 +274,7 @@ def _ptr(t):
 # raw launcher
 # ----------------------------------------------------------------------------------------------
 def spmm_raw(adj, x, which='fwd', y=None, noise=None, eps=0.0, acc_in=None, acc_out=None, want_y=True, chained=False,
-             noise_sumsq=None, noise_geom=None, axpy=None, x_row_bits=None, sum_in=None, row_scale=None, scale_flags=0):
+             noise_sumsq=None, noise_geom=None, axpy=None, x_row_bits=None, sum_in=None, row_scale=None, scale_flags=0, reg_sumsq=None):
     """Launch one CSR SpMM with optional fused epilogue.  `adj` is a PropGraph or DroppedView;
     `which` selects A ('fwd') or A^T ('bwd').  Returns y (or None when want_y=False).  (`chained` is accepted and ignored.)
     Column slices of a table (feature-sliced tables): `noise_sumsq` [n_rows] = squared norm of the FULL noise row, `noise_geom`
@@ -273,7 +283,9 @@ def spmm_raw(adj, x, which='fwd', y=None, noise=None, eps=0.0, acc_in=None, acc_
     `x_row_bits` = RowBits or None: a hint that the rows of x outside the bitmap are all zeros (sslrec_epilogue_t.x_row_bits).
     `sum_in` = up to 3 tables: acc_out = ((acc_in + sum_in[0]) + ...) + y (deferred layer sum; column-swept layouts only).
     `row_scale` [n_rows] + `scale_flags` (SCALE_PATTERN | SCALE_Y | SCALE_ACC): the factorized normalization of a layer chain
-    (sslrec_epilogue_t.scale_flags; column-swept layouts only)."""
+    (sslrec_epilogue_t.scale_flags; column-swept layouts only).
+    `reg_sumsq` = (ticket workspace, out [1], weight): the launch also writes out[0] = weight * sum(acc_in^2)
+    (sslrec_spmm_swept_step_f32; the caller has asked sslrec_swept_step_ok)."""
     view = adj if isinstance(adj, (DroppedView, RevaluedView)) else None
     graph = adj.graph if view is not None else adj
     plan = getattr(graph, which)
@@ -349,11 +361,27 @@ def spmm_raw(adj, x, which='fwd', y=None, noise=None, eps=0.0, acc_in=None, acc_
         ev0.record()                                                                               # launch-bound step to the kernel)
     if STAMPS is not None:
         STAMPS.attach_next(swept if swept is not None else lay, d, acc_out is not None, want_y, _entry_frac(view), None, len(sum_in or ()))
-    if swept is not None:       # output table fits the chip's LDS: column-swept kernel (spmm_swept.hip)
+    if reg_sumsq is not None and (swept is None or epi is None):
+        raise ValueError('reg_sumsq rides on a column-swept launch with an accumulator')
+    step = None
+    if reg_sumsq is not None:
+        step = _lib.SweptStepStruct(reg_sumsq[0].data_ptr(), reg_sumsq[1].data_ptr(), float(reg_sumsq[2]), _lib.STEP_SUMSQ)
+    elif (AXPY_BATCH and axpy is not None and swept is not None and swept.n_pass == 1 and not sum_in
+          and lib.sslrec_swept_step_ok(C.byref(swept.c_struct()))):
+        step = _lib.SweptStepStruct(None, None, 0.0, _lib.STEP_AXPY_BATCH)
+        AXPY_ROUTES['batched'] += 1
+    if axpy is not None and step is None:
+        AXPY_ROUTES['plain'] += 1
+    if swept is not None and step is not None:
+        rc = lib.sslrec_spmm_swept_step_f32(C.byref(swept.c_struct()), _ptr(col), _ptr(val), _ptr(w_len), x.data_ptr(), d,
+                                            _ptr(y) if want_y else None, C.byref(epi), C.byref(step), _stream())
+        _lib.check(rc, 'sslrec_spmm_swept_step_f32')
+    elif swept is not None:       # output table fits the chip's LDS: column-swept kernel (spmm_swept.hip)
         rc = lib.sslrec_spmm_swept_f32(C.byref(swept.c_struct()), _ptr(col), _ptr(val), _ptr(w_len), x.data_ptr(), d,
                                        _ptr(y) if want_y else None,
                                        C.byref(epi) if epi is not None else None, _stream())
         _lib.check(rc, 'sslrec_spmm_swept_f32')
+    if swept is not None:
         if PROFILE is not None:
             if prof:
                 ev1.record()
@@ -1142,13 +1170,29 @@ class _PropagateSumFn(torch.autograd.Function):
     def forward(ctx, e0, adj, layer_num, noises, eps, keep_layers, noise_sumsq, noise_geom, reg_weight):
         ctx.adj, ctx.layer_num, ctx.reg_weight = adj, layer_num, reg_weight
         e0 = _f32c(e0)
-        reg = ()
+        # deferred layer sum: the launches l < L write E_l only, the last one forms ((E0 + E1) + ...) + E_L -- the running sum's bits
+        # without its 2 (L - 1) table-sized writes and L - 1 reads (column-swept layouts; L - 1 tables fit sslrec_epilogue_t.sum_in)
+        plan_f = (adj.graph if isinstance(adj, (DroppedView, RevaluedView)) else adj).fwd
+        lay_f = plan_f.swept(e0.shape[1]) if DEFERRED_SUM and 2 <= layer_num <= MAX_SUM_IN + 1 else None
+        deferred = lay_f is not None and bool(_lib.load().sslrec_swept_deferred_sum_ok(C.byref(lay_f.c_struct())))
+        reg, reg_ride = (), None
         if reg_weight is not None:
             lib = _lib.load()
             ws = _ticket_ws(e0.device, lib.sslrec_sumsq_ws_bytes(), 'sumsq')
             out = torch.empty(1, dtype=torch.float32, device=e0.device)
-            _lib.check(lib.sslrec_sumsq_fwd_f32(e0.data_ptr(), e0.numel(), float(reg_weight), ws.data_ptr(), out.data_ptr(), _stream()),
-                       'sslrec_sumsq_fwd_f32')
+            # the regularizer rides on the first product (acc_out = E0 + A.E0 reads every row of E0 once in its flush) where that launch
+            # is the plain one-pass swept product with a running sum; every other case keeps the launch of its own
+            lay_r = None
+            if (REG_IN_FLUSH and layer_num >= 1 and noises is None and not keep_layers and noise_sumsq is None and noise_geom is None
+                    and not deferred):
+                lay_r = plan_f.swept(e0.shape[1])
+            if lay_r is not None and lay_r.n_pass == 1 and lib.sslrec_swept_step_ok(C.byref(lay_r.c_struct())):
+                reg_ride = (ws, out, float(reg_weight))
+                REG_ROUTES['flush'] += 1
+            else:
+                _lib.check(lib.sslrec_sumsq_fwd_f32(e0.data_ptr(), e0.numel(), float(reg_weight), ws.data_ptr(), out.data_ptr(), _stream()),
+                           'sslrec_sumsq_fwd_f32')
+                REG_ROUTES['kernel'] += 1
             reg = (out.reshape(()),)
             ctx.save_for_backward(e0)
         layers = [e0] if keep_layers else None
@@ -1157,11 +1201,6 @@ class _PropagateSumFn(torch.autograd.Function):
             return (e0.clone(),) + reg
         total = torch.empty_like(e0)
         x = e0
-        # deferred layer sum: the launches l < L write E_l only, the last one forms ((E0 + E1) + ...) + E_L -- the running sum's bits
-        # without its 2 (L - 1) table-sized writes and L - 1 reads (column-swept layouts; L - 1 tables fit sslrec_epilogue_t.sum_in)
-        plan_f = (adj.graph if isinstance(adj, (DroppedView, RevaluedView)) else adj).fwd
-        lay_f = plan_f.swept(e0.shape[1]) if DEFERRED_SUM and 2 <= layer_num <= MAX_SUM_IN + 1 else None
-        deferred = lay_f is not None and bool(_lib.load().sslrec_swept_deferred_sum_ok(C.byref(lay_f.c_struct())))
         # factorized normalization: launch 1 reads the values and writes the SCALED table r (.) E_1, the others add rows of the scaled
         # table (no value stream) and scale the row sum in their flush
         rsc = None if (deferred or keep_layers or noise_sumsq is not None or noise_geom is not None) else \
@@ -1182,7 +1221,8 @@ class _PropagateSumFn(torch.autograd.Function):
             else:
                 y = spmm_raw(adj, x, 'fwd', noise=nz, eps=eps, acc_in=e0 if l == 0 else total, acc_out=total, want_y=want_y,
                              chained=l > 0, noise_sumsq=nss, noise_geom=noise_geom, row_scale=rsc,
-                             scale_flags=0 if rsc is None else ((SCALE_PATTERN if l > 0 else 0) | (SCALE_Y if want_y else 0)))
+                             scale_flags=0 if rsc is None else ((SCALE_PATTERN if l > 0 else 0) | (SCALE_Y if want_y else 0)),
+                             reg_sumsq=reg_ride if l == 0 else None)
             if keep_layers:
                 layers.append(y)
             x = y

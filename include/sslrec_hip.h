@@ -878,6 +878,31 @@ int sslrec_edge_gate_bwd_f32(const int32_t *rowptr, const int32_t *col, const in
                              float zeta, float beta, float eps, const float *m, const float *s, const float *dinv, const float *dvals,
                              const float *dl0, float *dp, float *dq, float *dbias, float *dla_ws, float *n_ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * Lloyd's k-means of NCL (csrc/kmeans.hip), the loop of KMeansClustering.forward, models/aug_utils.py:149-156:
+ *     for i in range(1000):
+ *         dists = (embeds.view([-1, 1, d]) - centroids.view([1, -1, d])).square().sum(-1)
+ *         _, idxs = t.min(dists, dim=1)
+ *         newCents = t.zeros_like(centroids);  newCents.index_add_(0, idxs, embeds)
+ *         clustNums = t.zeros([K, 1]);         clustNums.index_add_(0, idxs, ones)
+ *         centroids = newCents / (clustNums + 1e-6)
+ * on X [N, d] fp32 row-major, N >= 1, d in {32, 64, 128}, K >= 1 with K * d * 4 <= 64 KiB.  Nothing of size N x K is written.  Distances
+ * in the difference form in fp32; among equal distances the LOWEST cluster index wins; no float atomics, every sum in an order that
+ * depends on (N, K, d) and idx only: two runs give the same bits.  An empty cluster gets the centroid 0 and the count 0.
+ * SSLREC_E_BADARG before any launch for a null pointer, a value outside these ranges, or X / cent not 16-byte aligned. */
+
+/* bytes of the workspace (slab partial sums and counts, changed-row counters); 0 for arguments out of range */
+size_t sslrec_kmeans_ws_bytes(int32_t N, int32_t K, int32_t d);
+
+/* cent [K, d]: the initial centroids on entry (t.rand([K, d]), :147), the final ones on return; idx [N] int32 and counts [K] (the
+ * integer cluster sizes as fp32, clustNums) are written.  Runs max_iter >= 1 iterations of three launches each on `stream`.  early_exit
+ * != 0: every `poll` (1 .. 64) iterations the host reads how many rows changed their cluster in each of them (one copy, one stream
+ * synchronisation) and stops after the first period in which some iteration changed none -- every further iteration would reproduce
+ * centroids, idx and counts bit for bit, so the result is that of max_iter iterations.  iters_run[0] (host memory) = iterations
+ * launched.  early_exit == 0: no copy, no synchronisation.  Not capturable into a hipGraph with early_exit. */
+int sslrec_kmeans_f32(const float *X, int32_t N, int32_t d, int32_t K, float *cent, int32_t *idx, float *counts, int32_t max_iter,
+                      int32_t early_exit, int32_t poll, int32_t *iters_run, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

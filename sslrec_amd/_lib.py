@@ -199,6 +199,8 @@ SIGNATURES = {
     'sslrec_edge_gate_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     'sslrec_edge_gate_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P,
                                            _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_kmeans_ws_bytes': (C.c_size_t, [_I, _I, _I]),
+    'sslrec_kmeans_f32': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_int32), _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

@@ -1,6 +1,6 @@
 """Augmentation modules feeding the hot path; same class names and call signatures as the
 reference's models/aug_utils.py (EdgeDrop :11-31, EmbedPerturb :118-132, SvdDecomposition
-:82-98, AdaptiveMask :52-80).  AdaptiveMask is the one exception to "same call signature": it takes the NODE table and folds in
+:82-98, AdaptiveMask :52-80, KMeansClustering :134-157).  AdaptiveMask is the one exception to "same call signature": it takes the NODE table and folds in
 the gathers its only caller does first (dccf.py:83-86), so no [nnz, d] tensor is ever built; the reference's two-tensor call raises
 a TypeError that says so.  The random draws are taken from the global torch CPU generator in exactly the
 reference's order and shapes (parity mode), unless `device_rng` is given (perf mode: a
@@ -160,3 +160,31 @@ class SvdDecomposition(nn.Module):
         u_mul_s = svd_u @ t.diag(s)
         v_mul_s = svd_v @ t.diag(s)
         return svd_u.T, svd_v.T, u_mul_s, v_mul_s
+
+
+class KMeansClustering(nn.Module):
+    """Lloyd's k-means over an embedding table (reference :134-157, used in NCL): forward(embeds) returns (centroids [K, d],
+    idxs [N] int64, clustNums [K, 1]) after `max_iter` = 1000 iterations from t.rand([K, d]) -- as ONE call, ops.kmeans
+    (csrc/kmeans.hip), which never forms the [N, K, d] distances, adds in a fixed order and stops once an iteration changes no
+    assignment (from there on every iteration reproduces its input bit for bit; `iters_run` tells how many ran).  Among equal
+    distances the lowest index wins, what t.min gives on the CPU.  The initial centroids are the reference's draw (:147) from the
+    CPU generator -- through the device replay when one is active -- or, with `device_rng`, a draw of the device's generator."""
+
+    def __init__(self, cluster_num, embedding_size, device_rng=False, max_iter=1000):
+        super().__init__()
+        self.cluster_num = cluster_num
+        self.embedding_size = embedding_size
+        self.device_rng = device_rng
+        self.max_iter = max_iter
+        self.iters_run = None
+
+    def draw_centroids(self, device):
+        shape = (self.cluster_num, self.embedding_size)
+        if self.device_rng:
+            return t.rand(shape, device=device)
+        return _pinned.rand_to(shape, device)
+
+    def forward(self, embeds):
+        from .. import ops
+        centroids, idxs, clustNums, self.iters_run = ops.kmeans(embeds, self.draw_centroids(embeds.device), self.max_iter)
+        return centroids, idxs, clustNums

@@ -1968,6 +1968,89 @@ def uniformity(x):
 
 
 # ----------------------------------------------------------------------------------------------
+# Lloyd's k-means of NCL (KMeansClustering.forward, aug_utils.py:147-157) without the [N, K, d] tensor (csrc/kmeans.hip)
+# ----------------------------------------------------------------------------------------------
+KMEANS_DIMS = (32, 64, 128)
+KMEANS_CENT_BYTES = 64 * 1024          # the centroids sit in LDS
+KMEANS_FUSED = os.environ.get('SSLREC_KMEANS_FUSED', '1') != '0'      # 0: the composed torch expression at every size (measurement)
+KMEANS_POLL = 8                        # iterations between two looks of the host at the changed-row counters (early exit)
+KMEANS_CHUNK_ELEMS = 1 << 22           # composed path: rows per chunk = this / (K d)
+
+
+def kmeans_fused_ok(K, d):
+    """shapes the kernels take: d in KMEANS_DIMS, K * d * 4 <= 64 KiB"""
+    return int(d) in KMEANS_DIMS and int(K) >= 1 and int(K) * int(d) * 4 <= KMEANS_CENT_BYTES
+
+
+def _kmeans_composed(x, cent, max_iter, early_exit, poll):
+    """the reference's iteration in torch, over row chunks (never the whole [N, K, d]); the lowest index among equal distances, and
+    sums by reductions only (no index_add_, whose float atomics depend on the order of arrival): two runs give the same bits"""
+    N, d = x.shape
+    K = cent.shape[0]
+    rows = max(1, KMEANS_CHUNK_ELEMS // (K * d))
+    ks = torch.arange(K, device=x.device)
+    prev, pending, it = None, [], 0
+    idx = counts = None
+    while it < max_iter:
+        idx = torch.empty(N, dtype=torch.int64, device=x.device)
+        sums = torch.zeros_like(cent)
+        for lo in range(0, N, rows):
+            xc = x[lo:lo + rows]
+            dist = (xc[:, None, :] - cent[None, :, :]).square().sum(-1)
+            lowest = dist.min(dim=1, keepdim=True).values
+            ic = torch.where(dist == lowest, ks, K).min(dim=1).values
+            ic = torch.where(ic == K, 0, ic)                     # (a row of NaN distances: cluster 0, like the kernel)
+            idx[lo:lo + rows] = ic
+            sums += ((ic[None, :] == ks[:, None]).to(x.dtype)[:, :, None] * xc[None, :, :]).sum(1)
+        counts = torch.bincount(idx, minlength=K)                # (integer atomics: exact)
+        cent = sums / (counts.to(x.dtype)[:, None] + 1e-6)
+        if early_exit:                                           # rows that changed cluster; iteration 0 counts every row
+            pending.append((idx != prev).sum() if prev is not None else torch.full((), N, dtype=torch.int64, device=x.device))
+        prev = idx
+        it += 1
+        if early_exit and it < max_iter and len(pending) == poll:
+            settled = bool((torch.stack(pending) == 0).any().item())
+            pending = []
+            if settled:
+                break
+    return cent, idx, counts.to(x.dtype).reshape(K, 1), it
+
+
+def kmeans(embeds, centroids0, max_iter=1000, early_exit=True, poll=None):
+    """The loop of KMeansClustering.forward (aug_utils.py:149-156) from the initial centroids `centroids0` [K, d] (:147) on
+    `embeds` [N, d]: returns (centroids [K, d], idx [N] int64, counts [K, 1], iters_run).  Not differentiable (ncl.py:27-28 calls it
+    on .detach()).  Distances in the difference form in fp32, the lowest index among equal distances, deterministic sums; an empty
+    cluster has centroid 0 and count 0.  early_exit: the host looks every `poll` iterations (default KMEANS_POLL) at how many rows
+    changed cluster and stops once an iteration changed none -- the result is bit for bit that of max_iter iterations (DESIGN 4.11);
+    iters_run = iterations actually run.  Shapes outside kmeans_fused_ok (and SSLREC_KMEANS_FUSED=0) run the composed expression over
+    row chunks."""
+    _need_gpu(embeds, centroids0)
+    if embeds.dim() != 2 or centroids0.dim() != 2 or embeds.shape[1] != centroids0.shape[1] or embeds.shape[0] < 1 or centroids0.shape[0] < 1:
+        raise ValueError('kmeans: embeds [N, d] and centroids0 [K, d] with N, K >= 1 expected, got %s and %s'
+                         % (tuple(embeds.shape), tuple(centroids0.shape)))
+    max_iter, poll = int(max_iter), int(KMEANS_POLL if poll is None else poll)
+    if max_iter < 1 or not 1 <= poll <= 64:
+        raise ValueError('kmeans: max_iter >= 1 and 1 <= poll <= 64 expected, got %d and %d' % (max_iter, poll))
+    with torch.no_grad():
+        x, cent = _f32c(embeds.detach()), _f32c(centroids0.detach())
+        (N, d), K = x.shape, cent.shape[0]
+        if not (KMEANS_FUSED and kmeans_fused_ok(K, d)) or N > 0x7fffffff:
+            return _kmeans_composed(x, cent, max_iter, bool(early_exit), poll)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        cent = cent.clone()                                      # the kernels work in place
+        lib = _lib.load()
+        ws = torch.empty(lib.sslrec_kmeans_ws_bytes(N, K, d) // 4 + 1, dtype=torch.float32, device=x.device)
+        idx = torch.empty(N, dtype=torch.int32, device=x.device)
+        counts = torch.empty(K, dtype=torch.float32, device=x.device)
+        iters = C.c_int32(0)
+        rc = lib.sslrec_kmeans_f32(x.data_ptr(), N, d, K, cent.data_ptr(), idx.data_ptr(), counts.data_ptr(), max_iter, int(bool(early_exit)),
+                                   poll, C.byref(iters), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_kmeans_f32')
+        return cent, idx.long(), counts.reshape(K, 1), int(iters.value)
+
+
+# ----------------------------------------------------------------------------------------------
 # the stacked parameter table [user_embeds; item_embeds] without the per-forward concatenation (reference lightgcn.py:34)
 # ----------------------------------------------------------------------------------------------
 def stacked_alias(u, i):

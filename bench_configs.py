@@ -100,6 +100,9 @@ def _cpu_step_baseline(tag, trn, mcfg, batch, budget_s):
     # all of them): the baseline is the best of a few thread counts, each tried while the budget lasts, and says which it used
     best, best_thr, n_steps = None, None, 0
     t_all = time.perf_counter()
+    # the caller's thread count goes back afterwards: os.cpu_count() can exceed the cores this process may use, and whatever runs next in
+    # the process would pay a parallel region of that many threads per host op
+    prev_threads = torch.get_num_threads()
     for thr in sorted({min(16, os.cpu_count()), min(64, os.cpu_count()), os.cpu_count()}):
         if best is not None and time.perf_counter() - t_all + 1.5 * best > budget_s:
             break
@@ -117,7 +120,7 @@ def _cpu_step_baseline(tag, trn, mcfg, batch, budget_s):
             n_steps += 1
             if dt < best:
                 best, best_thr = dt, thr
-    torch.set_num_threads(os.cpu_count())
+    torch.set_num_threads(prev_threads)
     return float(best), n_steps, best_thr
 
 

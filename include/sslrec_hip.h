@@ -903,6 +903,59 @@ size_t sslrec_kmeans_ws_bytes(int32_t N, int32_t K, int32_t d);
 int sslrec_kmeans_f32(const float *X, int32_t N, int32_t d, int32_t K, float *cent, int32_t *idx, float *counts, int32_t max_iter,
                       int32_t early_exit, int32_t poll, int32_t *iters_run, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * GFormer's anchor distances (csrc/bfs.hip), get_random_anchorset of models/general_cf/gformer.py:152-176:
+ *     graph = nx.Graph();  graph.add_edges_from(zip(rows, cols))
+ *     dicts_dict[node] = nx.single_source_shortest_path_length(graph, node, cutoff=None)       for every anchor
+ *     dists_array[i, j] = 1 / (dist + 1)                                                        in a Python double loop
+ * as one level-synchronous multi-source BFS with a 64-bit reached mask per node and 64 anchors, pull form, over the CSR of the pattern
+ * (rowptr [n + 1], col [E], n x n, SYMMETRIC -- not checked; duplicate entries are harmless).  long_rows: the rows of more than
+ * SSLREC_EDGE_LONG_ROW entries (nullable when n_long = 0), which get a workgroup each.  1 <= A <= 256, 1 <= n < 2^31; anchors [A] int32,
+ * distinct.  hops [n, A] int16 row-major: the hop count of node n from anchor a, 0 for the anchor itself, -1 for an unreached node; the
+ * reference's weight is hop < 0 ? 0 : 1 / (hop + 1).  Integers only: exact, and two runs give the same bits.
+ * SSLREC_E_BADARG before any launch for a null pointer or a value outside these ranges. */
+
+/* bytes of the workspace (two reached buffers, the per-level counters); 0 for arguments out of range */
+size_t sslrec_anchor_hops_ws_bytes(int32_t n, int32_t A);
+
+/* Every `poll` (1 .. 64) levels the host reads how many rows gained a bit in each of them (one copy, one stream synchronisation) and
+ * stops after the first period in which some level changed nothing; later levels are the identity, so the result does not depend on
+ * `poll`.  levels[0] (host) = the levels that changed something, converged[0] (host) = 1 -- or, when 32766 levels have all changed
+ * something, converged[0] = 0: the caller must treat that as an error (int16 would be exceeded next), nothing saturates silently. */
+int sslrec_anchor_hops(const int32_t *rowptr, const int32_t *col, int32_t n, const int32_t *long_rows, int32_t n_long, const int32_t *anchors,
+                       int32_t A, int16_t *hops, int32_t poll, int32_t *levels, int32_t *converged, void *ws, void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * GFormer's position features (csrc/pnn.hip), PNNLayer.forward of models/general_cf/gformer.py:202-218:
+ *     set_ids_reshape = embeds[anchor_set_id].repeat(N, 1).reshape(-1, A, d);  messages = set_ids_reshape * dists_array.T.unsqueeze(2)
+ *     self_feature = embeds.repeat(A, 1).reshape(-1, A, d)
+ *     outposition1 = t.mean(self.linear_hidden(t.cat((messages, self_feature), dim=-1)), dim=1)
+ * with the Linear commuted past the mean: Z [N, 2d] = [s, u], s[n] = (1 / A) sum_a w[n, a] X[anchors[a]] with w decoded from hops
+ * (sslrec_anchor_hops), u[n] = (1 / A) sum_{a < A} X[(n A + a) mod N] -- element [n, a] of the reference's self_feature is that row, not
+ * row n.  The caller applies the Linear.  X [N, d] fp32 row-major, 16-byte aligned; d in {32, 64, 128}, 1 <= A <= 256, A d 4 <= 128 KiB,
+ * 1 <= N < 2^31; anchors [A] int32 in [0, N) (distinct in the model; a repeated id is handled exactly); hops [N, A] int16.  Nothing of size N x A x d or N x A floats is written, no
+ * float atomics, every sum in a fixed order.  SSLREC_E_BADARG before any launch for a null pointer or a shape outside these ranges.  The ids live on
+ * the device and are NOT checked: an id outside [0, N) gives an undefined result (forward and backward), no error code; no memory outside
+ * the tables is touched. */
+int sslrec_pnn_fwd_f32(const float *X, int32_t N, int32_t d, const int32_t *anchors, int32_t A, const int16_t *hops, float *Z, void *stream);
+
+/* bytes of the backward's workspace (slab partial sums of the anchor rows' gradient and their total); 0 for shapes out of range */
+size_t sslrec_pnn_bwd_ws_bytes(int32_t N, int32_t A, int32_t d);
+
+/* dX [N, d] (written, not added to) from gZ [N, 2d]: the window half as a gather, dX[m] = (1 / A) sum_{j < A} gu[(m + j N) / A], then
+ * dX[anchors[a]] += (1 / A) sum_n w[n, a] gs[n]. */
+int sslrec_pnn_bwd_f32(const float *gZ, int32_t N, int32_t d, const int32_t *anchors, int32_t A, const int16_t *hops, float *dX, void *ws,
+                       void *stream);
+
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * Per-entry attention of GFormer's LocalGraph (csrc/gt.hip), models/general_cf/gformer.py:235-255 with :351-352:
+ *     embeds_l2, atten = self.gt_layer(add_adj, embeds);  att_edge = t.sum(atten, dim=-1)
+ * out[k] = sum_h exp(clamp(<Q[r, h], K[c, h]>, -10, 10)) / (Z[r, h] + 1e-8) for every CSR position k = (r, c) of the pattern; arguments
+ * and shapes as sslrec_gt_fwd_f32.  Forward only.  z_ws: n * heads floats (sslrec_gt_scores_ws_bytes; 0 for a shape without a kernel). */
+size_t sslrec_gt_scores_ws_bytes(int32_t n, int32_t d, int32_t heads);
+int sslrec_gt_scores_f32(const int32_t *rowptr, const int32_t *col, int32_t n, const int32_t *long_rows, int32_t n_long, const float *Q,
+                         const float *K, int32_t d, int32_t heads, float *out, float *z_ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,13 @@ SIGNATURES = {
                                            _P, _P, _P, _P, _P, _P, _P]),
     'sslrec_kmeans_ws_bytes': (C.c_size_t, [_I, _I, _I]),
     'sslrec_kmeans_f32': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, C.POINTER(C.c_int32), _P, _P]),
+    'sslrec_anchor_hops_ws_bytes': (C.c_size_t, [_I, _I]),
+    'sslrec_anchor_hops': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P]),
+    'sslrec_pnn_bwd_ws_bytes': (C.c_size_t, [_I, _I, _I]),
+    'sslrec_pnn_fwd_f32': (C.c_int, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    'sslrec_pnn_bwd_f32': (C.c_int, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'sslrec_gt_scores_ws_bytes': (C.c_size_t, [_I, _I, _I]),
+    'sslrec_gt_scores_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

@@ -235,6 +235,43 @@ __global__ __launch_bounds__(256) void gt_dkv_kernel(const int32_t *__restrict__
     if (dV) dV[(size_t)c * L + lig] = acc_v;
 }
 
+// ---- per-entry attention summed over the heads (GFormer's LocalGraph, gformer.py:351-352: att_edge = t.sum(atten, dim=-1)) ---------
+// Two passes over the rows with the forward's walk.  WRITE = false: Z[r, h]; WRITE = true: out[k] = sum_h w_kh / (Z[r, h] + 1e-8) for every
+// CSR position k of the row.  The heads' values sit on the first lane of each head; group_sum<L> adds them in a fixed order.
+template <int D, int DH, bool LONG, bool WRITE>
+__global__ __launch_bounds__(256) void gt_scores_kernel(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const int n,
+                                                        const int32_t *__restrict__ long_rows, const float4 *__restrict__ Q,
+                                                        const float4 *__restrict__ K, float *__restrict__ Z, float *__restrict__ out) {
+    constexpr int L = D / 4, HL = DH / 4, H = D / DH, STEP = LONG ? 256 / L : 1;
+    __shared__ float lds1[LONG ? 256 : 1];
+    int r, k, k1;
+    if (!gt_row<L, LONG>(rowptr, n, long_rows, r, k, k1)) return;
+    const int lig = threadIdx.x % L;
+    const float4 q = Q[(size_t)r * L + lig];
+    if constexpr (WRITE) {
+        const float den = Z[(size_t)r * H + lig / HL] + GT_EPS;
+        for (; k < k1; k += STEP) {
+            const int c = col[k];
+            const float s = group_sum<HL>(dot4(q, K[(size_t)c * L + lig]));
+            const float a = expf(fminf(fmaxf(s, -GT_CLAMP), GT_CLAMP)) / den;
+            const float tot = group_sum<L>(lig % HL == 0 ? a : 0.f);
+            if (lig == 0) out[k] = tot;
+        }
+    } else {
+        float z = 0.f;
+        for (; k < k1; k += STEP) {
+            const int c = col[k];
+            const float s = group_sum<HL>(dot4(q, K[(size_t)c * L + lig]));
+            z += expf(fminf(fmaxf(s, -GT_CLAMP), GT_CLAMP));
+        }
+        if constexpr (LONG) {
+            z = gt_combine1<L>(z, lds1);
+            if (threadIdx.x >= L) return;
+        }
+        if (lig % HL == 0) Z[(size_t)r * H + lig / HL] = z;
+    }
+}
+
 inline bool gt_shape_ok(int d, int heads) {
     if (d != 32 && d != 64 && d != 128) return false;
     if (heads < 1 || d % heads != 0) return false;
@@ -282,6 +319,37 @@ int sslrec_gt_fwd_f32(const int32_t *rowptr, const int32_t *col, int32_t n, cons
         if (n_long > 0)                                                                                                                   \
             hipLaunchKernelGGL((gt_fwd_kernel<D, DH, true>), dim3((unsigned)n_long), dim3(256), 0, st, rowptr, col, (int)n, long_rows,    \
                                (const float4 *)Q, (const float4 *)K, (const float4 *)V, (float4 *)Y, Z);                                  \
+    }
+    GT_BY_SHAPE(d, d / heads, CALL)
+#undef CALL
+    SSLREC_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t sslrec_gt_scores_ws_bytes(int32_t n, int32_t d, int32_t heads) {
+    if (n < 1 || !gt_shape_ok(d, heads)) return 0;
+    return (size_t)n * heads * sizeof(float);
+}
+
+int sslrec_gt_scores_f32(const int32_t *rowptr, const int32_t *col, int32_t n, const int32_t *long_rows, int32_t n_long, const float *Q,
+                         const float *K, int32_t d, int32_t heads, float *out, float *z_ws, void *stream) {
+    if (!rowptr || !col || !Q || !K || !out || !z_ws || n < 0 || n_long < 0 || (n_long > 0 && !long_rows) || !gt_shape_ok(d, heads))
+        return SSLREC_E_BADARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_long == 0) long_rows = nullptr;
+#define CALL(D, DH)                                                                                                                       \
+    {                                                                                                                                     \
+        hipLaunchKernelGGL((gt_scores_kernel<D, DH, false, false>), dim3(gt_blocks(n, 256 / (D / 4))), dim3(256), 0, st, rowptr, col,     \
+                           (int)n, long_rows, (const float4 *)Q, (const float4 *)K, z_ws, out);                                           \
+        if (n_long > 0)                                                                                                                   \
+            hipLaunchKernelGGL((gt_scores_kernel<D, DH, true, false>), dim3((unsigned)n_long), dim3(256), 0, st, rowptr, col, (int)n,     \
+                               long_rows, (const float4 *)Q, (const float4 *)K, z_ws, out);                                               \
+        hipLaunchKernelGGL((gt_scores_kernel<D, DH, false, true>), dim3(gt_blocks(n, 256 / (D / 4))), dim3(256), 0, st, rowptr, col,      \
+                           (int)n, long_rows, (const float4 *)Q, (const float4 *)K, z_ws, out);                                           \
+        if (n_long > 0)                                                                                                                   \
+            hipLaunchKernelGGL((gt_scores_kernel<D, DH, true, true>), dim3((unsigned)n_long), dim3(256), 0, st, rowptr, col, (int)n,      \
+                               long_rows, (const float4 *)Q, (const float4 *)K, z_ws, out);                                               \
     }
     GT_BY_SHAPE(d, d / heads, CALL)
 #undef CALL

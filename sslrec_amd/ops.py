@@ -2051,6 +2051,242 @@ def kmeans(embeds, centroids0, max_iter=1000, early_exit=True, poll=None):
 
 
 # ----------------------------------------------------------------------------------------------
+# GFormer (gformer.py): hop counts from the anchors by a bit-parallel multi-source BFS (csrc/bfs.hip), the PNN layer's position
+# features without its [N, A, d] tensors (csrc/pnn.hip), and the per-entry attention of LocalGraph (csrc/gt.hip)
+# ----------------------------------------------------------------------------------------------
+ANCHOR_MAX = 256                       # anchors the kernels take (four 64-bit words per node)
+ANCHOR_MAX_LEVEL = 32766               # levels after which a search that still changes something is an error (int16 hops)
+ANCHOR_HOPS_POLL = 8                   # levels between two looks of the host at the per-level counters
+ANCHOR_HOPS_FUSED = os.environ.get('SSLREC_ANCHOR_HOPS_FUSED', '1') != '0'      # 0: the composed torch loop at every size (measurement)
+PNN_DIMS = (32, 64, 128)
+PNN_LDS_BYTES = 128 * 1024
+PNN_FUSED = os.environ.get('SSLREC_PNN_FUSED', '1') != '0'                      # 0: the composed torch expression at every size
+EDGE_SCORES_FUSED = os.environ.get('SSLREC_EDGE_SCORES_FUSED', '1') != '0'
+
+
+def _pattern_csr(adj_or_pattern, what):
+    """(rowptr int32 [n + 1], col int32 [E], long_rows int32, n, device, coo) of an EdgePattern, or of the forward plan of a graph /
+    torch sparse adjacency (square); coo() -> (rows, cols) int64 in CSR order"""
+    if isinstance(adj_or_pattern, EdgePattern):
+        p = adj_or_pattern
+        return p.rowptr, p.col, p.long_rows, p.n, p.device, p.coo
+    graph = _pattern_graph(adj_or_pattern, what)
+    plan = _plan_of(graph, 'fwd', what)
+    if plan.n_rows != plan.n_cols:
+        raise ValueError('%s: a square pattern expected, got %d x %d' % (what, plan.n_rows, plan.n_cols))
+    csr = plan.device_csr()
+    return csr['rowptr'], csr['col'], csr['long_rows'], plan.n_rows, plan.device, lambda: (csr['row_of_entry'].long(), csr['col'].long())
+
+
+def _anchor_ids(anchors, n, what, distinct=True):
+    """the anchors as a validated CPU int64 tensor: 1-d, inside [0, n), distinct (unless distinct=False)"""
+    a = torch.as_tensor(np.asarray(anchors.detach().cpu()) if torch.is_tensor(anchors) else np.asarray(anchors)).long().reshape(-1)
+    if a.numel() < 1:
+        raise ValueError('%s: at least one anchor expected' % what)
+    if int(a.min()) < 0 or int(a.max()) >= n:
+        raise ValueError('%s: an anchor lies outside [0, %d)' % (what, n))
+    if distinct and torch.unique(a).numel() != a.numel():
+        raise ValueError('%s: the anchors must be distinct' % what)
+    return a
+
+
+def hop_weights(hops, dtype=torch.float32):
+    """the reference's weights from hop counts: float32(1 / (hop + 1)), 0 for an unreached node (gformer.py:172-174, :205), as `dtype`"""
+    w = (1.0 / (hops.double() + 1.0)).float()
+    return torch.where(hops < 0, torch.zeros((), dtype=torch.float32, device=hops.device), w).to(dtype)
+
+
+def _anchor_hops_composed(rows, cols, n, anchors, max_level=ANCHOR_MAX_LEVEL):
+    """the same level-synchronous search with torch ops, 64 anchors at a time: (hops int16 [n, A], levels that changed something)"""
+    dev = rows.device
+    A = anchors.numel()
+    hops = torch.full((n, A), -1, dtype=torch.int16, device=dev)
+    most = 0
+    for lo in range(0, A, 64):
+        anc = anchors[lo:lo + 64].to(dev)
+        ar = torch.arange(anc.numel(), device=dev)
+        reached = torch.zeros(n, anc.numel(), dtype=torch.bool, device=dev)
+        reached[anc, ar] = True
+        h = torch.full((n, anc.numel()), -1, dtype=torch.int16, device=dev)
+        h[anc, ar] = 0
+        level = 0
+        while True:
+            seen = torch.zeros(n, anc.numel(), dtype=torch.int32, device=dev).index_add_(0, rows, reached[cols].to(torch.int32)) > 0
+            new = seen & ~reached
+            if not bool(new.any()):
+                break
+            level += 1
+            if level >= max_level:
+                raise RuntimeError('anchor_hops: the search has not converged after %d levels' % max_level)
+            h[new] = level
+            reached |= new
+        hops[:, lo:lo + 64] = h
+        most = max(most, level)
+    return hops, most
+
+
+def anchor_hops_fused_ok(n, A):
+    """shapes csrc/bfs.hip takes: 1 <= A <= 256 anchors, 1 <= n < 2^31 nodes"""
+    return 1 <= int(A) <= ANCHOR_MAX and 1 <= int(n) < 2 ** 31 - 1
+
+
+def anchor_hops(adj_or_pattern, anchors, poll=None, return_levels=False):
+    """hops int16 [N, A]: the number of edges on a shortest path from anchor a to node n in the pattern of `adj_or_pattern` (a
+    graph.EdgePattern, a PropGraph / RevaluedView, or a torch sparse adjacency), 0 for the anchor itself, -1 for a node it does not
+    reach -- what gformer.py:152-176 computes with one networkx BFS per anchor; the reference's `dists_array` is the transpose as
+    float64 weights 1 / (hop + 1) (ops.hop_weights).  The pattern must be SYMMETRIC, as the reference's nx.Graph makes it; that is
+    not checked.  `anchors`: A distinct node ids (ValueError otherwise).  Exact (integers only).  The host looks every `poll` levels
+    (default ANCHOR_HOPS_POLL) at how many rows gained an anchor and stops after a level that changed nothing; the result does not
+    depend on `poll`.  A search that still changes something after 32766 levels raises.  1 <= A <= 256 runs csrc/bfs.hip; anything
+    else (and SSLREC_ANCHOR_HOPS_FUSED=0) runs a composed torch loop with the same result.  return_levels: (hops, levels that changed
+    something)."""
+    rowptr, col, long_rows, n, dev, coo = _pattern_csr(adj_or_pattern, 'anchor_hops')
+    if torch.device(dev).type != 'cuda':
+        raise RuntimeError('sslrec_amd kernels run on a HIP device only (got a %s pattern); there is no CPU fallback by design' % (dev,))
+    ids = _anchor_ids(anchors, n, 'anchor_hops')
+    A = ids.numel()
+    poll = int(ANCHOR_HOPS_POLL if poll is None else poll)
+    if not 1 <= poll <= 64:
+        raise ValueError('anchor_hops: 1 <= poll <= 64 expected, got %d' % poll)
+    with torch.no_grad():
+        if not (ANCHOR_HOPS_FUSED and anchor_hops_fused_ok(n, A)):
+            rows, cols = coo()
+            hops, levels = _anchor_hops_composed(rows, cols, n, ids)
+            return (hops, levels) if return_levels else hops
+        lib = _lib.load()
+        anc = ids.to(torch.int32).to(dev)
+        hops = torch.empty(n, A, dtype=torch.int16, device=dev)
+        ws = torch.empty(lib.sslrec_anchor_hops_ws_bytes(n, A) // 8 + 1, dtype=torch.int64, device=dev)
+        levels, converged = C.c_int32(0), C.c_int32(0)
+        rc = lib.sslrec_anchor_hops(rowptr.data_ptr(), col.data_ptr() if col.numel() else ws.data_ptr(), n,
+                                    long_rows.data_ptr() if long_rows.numel() else None, long_rows.numel(), anc.data_ptr(), A,
+                                    hops.data_ptr(), poll, C.byref(levels), C.byref(converged), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_anchor_hops')
+        if not converged.value:
+            raise RuntimeError('anchor_hops: the search has not converged after %d levels' % ANCHOR_MAX_LEVEL)
+        return (hops, int(levels.value)) if return_levels else hops
+
+
+def anchor_position_fused_ok(d, A):
+    """shapes csrc/pnn.hip takes: d in {32, 64, 128}, 1 <= A <= 256 anchors whose rows fit 128 KiB of LDS"""
+    return int(d) in PNN_DIMS and 1 <= int(A) <= ANCHOR_MAX and int(A) * int(d) * 4 <= PNN_LDS_BYTES
+
+
+def _anchor_position_composed(x, anchor_ids, hops):
+    """[s, u] [N, 2d] in torch, any dtype and device: the collapsed form of gformer.py:202-218 with the cyclic window of the
+    reference's repeat / reshape -- s = w @ x[anchors] / A, u[n] = sum_a x[(n A + a) mod N] / A as A row gathers, never an [N, A, d]"""
+    N, d = x.shape
+    A = anchor_ids.numel()
+    w = hop_weights(hops, x.dtype)
+    s = (w @ x[anchor_ids.long()]) / A
+    start = (torch.arange(N, device=x.device, dtype=torch.int64) * A) % N
+    u = torch.zeros_like(x)
+    for a in range(A):
+        u = u + x[(start + a) % N]
+    return torch.cat([s, u / A], dim=1)
+
+
+class _AnchorPositionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, anchors, hops):
+        x = _f32c(x)
+        if x.data_ptr() % 16:
+            x = x.clone()
+        N, d = x.shape
+        z = torch.empty(N, 2 * d, dtype=torch.float32, device=x.device)
+        rc = _lib.load().sslrec_pnn_fwd_f32(x.data_ptr(), N, d, anchors.data_ptr(), anchors.numel(), hops.data_ptr(), z.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_pnn_fwd_f32')
+        ctx.anchors, ctx.hops, ctx.shape = anchors, hops, (N, d)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        gz = _f32c(gz)
+        if gz.data_ptr() % 16:
+            gz = gz.clone()
+        N, d = ctx.shape
+        A = ctx.anchors.numel()
+        lib = _lib.load()
+        dx = torch.empty(N, d, dtype=torch.float32, device=gz.device)
+        ws = torch.empty(lib.sslrec_pnn_bwd_ws_bytes(N, A, d) // 4 + 1, dtype=torch.float32, device=gz.device)
+        rc = lib.sslrec_pnn_bwd_f32(gz.data_ptr(), N, d, ctx.anchors.data_ptr(), A, ctx.hops.data_ptr(), dx.data_ptr(), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_pnn_bwd_f32')
+        return dx, None, None
+
+
+def anchor_position_features(x, anchor_ids, hops):
+    """z [N, 2d] = [s, u], the two feature halves of GFormer's PNNLayer (gformer.py:202-218) with its Linear(2d, d) commuted past the
+    mean over the anchors -- the model applies F.linear(z, linear_hidden.weight, linear_hidden.bias):
+        s[n] = (1 / A) sum_a w[n, a] x[anchor_ids[a]],  w = float32(1 / (hops[n, a] + 1)), 0 where hops[n, a] < 0 (ops.anchor_hops)
+        u[n] = (1 / A) sum_{a < A} x[(n A + a) mod N]
+    The window in u is what the reference's `embeds.repeat(A, 1).reshape(-1, A, d)` holds at [n, a]: NOT row n.  For A = 1
+    the reference's `.squeeze()` drops the anchor axis and `mean(dim=1)` then averages over the features; this op is defined by the
+    un-squeezed expression.  `anchor_ids`: A ids in [0, N) (distinct in the model; a repeated id is handled exactly) -- validated when given
+    on the host; an int32 DEVICE tensor is trusted (the model validates once per epoch): an id outside [0, N) in it gives an undefined
+    RESULT without an error (the kernels never touch memory outside the tables).  `hops`: int16 [N, A].  Differentiable in x; no float atomics, two runs give the
+    same bits; nothing of size N x A x d is stored.  d in {32, 64, 128} with A <= 256 and A d 4 <= 128 KiB run csrc/pnn.hip
+    (anchor_position_fused_ok); other shapes, and SSLREC_PNN_FUSED=0, run the composed torch expression."""
+    _need_gpu(x, hops)
+    if x.dim() != 2 or hops.dim() != 2 or hops.shape[0] != x.shape[0] or hops.dtype != torch.int16:
+        raise ValueError('anchor_position_features: x [N, d] and hops int16 [N, A] expected, got %s and %s %s'
+                         % (tuple(x.shape), hops.dtype, tuple(hops.shape)))
+    N, d = x.shape
+    if torch.is_tensor(anchor_ids) and anchor_ids.is_cuda and anchor_ids.dtype == torch.int32:
+        anc = anchor_ids.reshape(-1).contiguous()
+    else:
+        anc = _anchor_ids(anchor_ids, N, 'anchor_position_features', distinct=False).to(torch.int32).to(x.device)
+    A = anc.numel()
+    if hops.shape[1] != A or N < 1:
+        raise ValueError('anchor_position_features: %d anchors for hops of shape %s' % (A, tuple(hops.shape)))
+    hops = hops.contiguous()
+    if not (PNN_FUSED and anchor_position_fused_ok(d, A)) or N >= 2 ** 31 - 1:
+        return _anchor_position_composed(x.float(), anc, hops)
+    return _AnchorPositionFn.apply(x.float(), anc, hops)
+
+
+def _edge_attention_scores_composed(pattern, q, k, head_num):
+    """att.sum(-1) of gformer.py:235-250 on the node tables, entries in the order of pattern.coo()"""
+    n, d = q.shape
+    rows, cols = pattern.coo()
+    dh = d // head_num
+    # (an element-wise product and a sum, not einsum: einsum turns 'ehd, ehd -> eh' into a batched GEMM of E * H batches of 1 x dh x 1)
+    att = torch.exp(torch.clamp((q[rows].view(-1, head_num, dh) * k[cols].view(-1, head_num, dh)).sum(-1), -10.0, 10.0))
+    norm = torch.zeros(n, head_num, dtype=q.dtype, device=q.device).index_add_(0, rows, att)[rows]
+    return (att / (norm + 1e-8)).sum(-1)
+
+
+def edge_attention_scores(pattern, q, k, head_num):
+    """fp32 [E]: per entry (r, c) of `pattern`, in the order of pattern.coo(), sum over the heads of exp(clamp(<q[r, h], k[c, h]>, -10, 10))
+    / (row sum of the exponentials + 1e-8) -- `t.sum(atten, dim=-1)` of GFormer's LocalGraph (gformer.py:235-255, :351-352), from the
+    projected NODE tables as in ops.edge_attention.  Forward only (the reference detaches it).  The shapes of
+    edge_attention_fused_ok run csrc/gt.hip; any other shape runs the composed torch expression."""
+    _need_gpu(q, k)
+    if not isinstance(pattern, EdgePattern):
+        pattern = pattern_of(pattern)
+    head_num = int(head_num)
+    if q.dim() != 2 or q.shape != k.shape or q.shape[0] != pattern.n:
+        raise ValueError('edge_attention_scores: tables %s / %s for a pattern of %d nodes' % (tuple(q.shape), tuple(k.shape), pattern.n))
+    d = q.shape[1]
+    if head_num < 1 or d % head_num != 0:
+        raise ValueError('edge_attention_scores: the embedding size %d is not a multiple of head_num = %d' % (d, head_num))
+    with torch.no_grad():
+        q, k = _f32c(q.detach().float()), _f32c(k.detach().float())
+        if not (EDGE_SCORES_FUSED and edge_attention_fused_ok(d, head_num)):
+            return _edge_attention_scores_composed(pattern, q, k, head_num)
+        out = torch.empty(pattern.nnz, dtype=torch.float32, device=q.device)
+        if pattern.n > 0 and pattern.nnz > 0:
+            lib = _lib.load()
+            z = torch.empty(lib.sslrec_gt_scores_ws_bytes(pattern.n, d, head_num) // 4 + 1, dtype=torch.float32, device=q.device)
+            p = pattern
+            rc = lib.sslrec_gt_scores_f32(p.rowptr.data_ptr(), p.col.data_ptr(), p.n, _ptr(p.long_rows) if p.long_rows.numel() else None,
+                                          p.long_rows.numel(), q.data_ptr(), k.data_ptr(), d, head_num, out.data_ptr(), z.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_gt_scores_f32')
+        return out
+
+
+# ----------------------------------------------------------------------------------------------
 # the stacked parameter table [user_embeds; item_embeds] without the per-forward concatenation (reference lightgcn.py:34)
 # ----------------------------------------------------------------------------------------------
 def stacked_alias(u, i):

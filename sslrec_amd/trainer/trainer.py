@@ -1,8 +1,8 @@
 """Training loop of the general-CF scenario; same public surface as the reference's `Trainer`
 (trainer/trainer.py:39-196): `create_optimizer`, `train_epoch`, `train` (optional early stop on
 the first configured metric), `evaluate`, `test`, `save_model`, `load_model`; per step
-zero_grad -> cal_loss -> backward -> step.  Of the eleven model-specific trainers upstream, AutoCF's and
-AdaGCL's are here (`AutoCFTrainer`, `AdaGCLTrainer`); the others belong to models outside this path."""
+zero_grad -> cal_loss -> backward -> step.  Of the eleven model-specific trainers upstream, AutoCF's, GFormer's and
+AdaGCL's are here (`AutoCFTrainer`, `GFormerTrainer`, `AdaGCLTrainer`); the others belong to models outside this path."""
 import os
 import time
 from copy import deepcopy
@@ -373,6 +373,67 @@ class AutoCFTrainer(Trainer):
                 infomax = -samp_scores.mean()
                 loss = loss + infomax
                 loss_dict['infomax_loss'] = infomax
+            self._backward(loss)
+            self.optimizer.step()
+            kept.append((loss.detach().reshape(()), {k: (v.detach().reshape(()).to(loss.dtype) if torch.is_tensor(v)
+                                                         else torch.tensor(float(v), dtype=loss.dtype, device=loss.device))
+                                                     for k, v in loss_dict.items()}))
+        loss_log, ep_loss = {}, 0.0
+        if kept:
+            flat = torch.stack([x for loss, parts in kept for x in [loss] + list(parts.values())]).double().cpu().tolist()      # one synchronisation per epoch
+            pos = 0
+            for _, parts in kept:
+                ep_loss += flat[pos]
+                for j, name in enumerate(parts):
+                    loss_log[name] = loss_log.get(name, 0.0) + flat[pos + 1 + j] / n_batches
+                pos += 1 + len(parts)
+        self.step_losses = [sorted(parts) for _, parts in kept]          # names logged by every step of the last epoch
+        steps = max(1, len(loader.dataset) // configs['train']['batch_size'])
+        writer.add_scalar('Loss/train', ep_loss / steps, epoch_idx)
+        self.logger.log_loss(epoch_idx, loss_log, save_to_log=bool(configs['train']['log_loss']))
+
+
+class GFormerTrainer(Trainer):
+    """reference trainer/trainer.py:253-296: `sample_negs`, then `model.preSelect_anchor_set()` once per epoch; every
+    `model.fix_steps` steps `model.localGraph` scores the entries of a widened adjacency and `model.masker` draws the encoder / decoder /
+    sub / cmp graphs from them; every step is cal_loss -> zero_grad -> backward -> step.  All draws of the epoch are numpy's global
+    generator, in the reference's order: the negative sampler's, the anchors', the masker's.  As in `_train_epoch_eager`, the step's 0-d
+    tensors are read once at the end of the epoch and summed on the host in the reference's order.  train.hip_graph is refused: the
+    resampling steps draw on the host and build new graphs, which a captured step cannot do.  The model makes no torch draw while
+    training, so the host generator replay is not switched on for this trainer."""
+
+    def __init__(self, data_handler, logger):
+        super().__init__(data_handler, logger)
+        self.handler = data_handler
+        self.user = configs['data']['user_num']
+        self.item = configs['data']['item_num']
+        self.latdim = configs['model']['embedding_size']
+        self.fixSteps = configs['model']['fix_steps']
+        if configs['train'].get('hip_graph'):
+            raise NotImplementedError('train.hip_graph is not supported by GFormerTrainer: every model.fix_steps steps the step draws on '
+                                      'the host and rebuilds its graphs')
+
+    @log_exceptions
+    def train(self, model):
+        return self._train(model)
+
+    def train_epoch(self, model, epoch_idx):
+        model.train()
+        loader = self.data_handler.train_dataloader
+        loader.dataset.sample_negs()
+        model.preSelect_anchor_set()
+        n_batches = len(loader)
+        kept = []
+        self.resampled_steps = []
+        encoderAdj = decoderAdj = sub = cmp = None
+        for i, tem in enumerate(loader):
+            batch_data = [x.long().to(configs['device']) for x in tem]
+            if i % self.fixSteps == 0:
+                att_edge, add_adj = model.localGraph(self.handler.torch_adj, model.getEgoEmbeds(), self.handler)
+                encoderAdj, decoderAdj, sub, cmp = model.masker(add_adj, att_edge)
+                self.resampled_steps.append(i)
+            loss, loss_dict = model.cal_loss(batch_data, encoderAdj, decoderAdj, sub, cmp)
+            self.optimizer.zero_grad()
             self._backward(loss)
             self.optimizer.step()
             kept.append((loss.detach().reshape(()), {k: (v.detach().reshape(()).to(loss.dtype) if torch.is_tensor(v)

@@ -956,6 +956,69 @@ size_t sslrec_gt_scores_ws_bytes(int32_t n, int32_t d, int32_t heads);
 int sslrec_gt_scores_f32(const int32_t *rowptr, const int32_t *col, int32_t n, const int32_t *long_rows, int32_t n_long, const float *Q,
                          const float *K, int32_t d, int32_t heads, float *out, float *z_ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * MHCN's row-wise kernels (csrc/mhcn.hip), models/social/mhcn.py.  Tables are [N, d] fp32 row-major, 16-byte aligned, d in {32, 64, 128},
+ * 1 <= N < 2^31.  No float atomics; every sum over rows is formed from per-workgroup partials in a fixed order, so two calls give the
+ * same bits.  SSLREC_E_BADARG before any launch for a null pointer, a misaligned table or a shape outside these ranges.
+ *
+ * Self-gating units (csrc/mhcn_gate.hip), mhcn.py:34-52:  gates = t.sigmoid(self.gatingC(em));  return em * gates
+ * for C <= 4 gates sharing one table: Y_c = X (.) sigmoid(X W_c^T + b_c) in ONE launch on the exact-fp32 MFMA.  Wt [C, d, d]: the
+ * TRANSPOSED weights, Wt[c][i][k] = W_c[k][i] for nn.Linear's out x in weight W_c; B [C, d] the biases (16-byte aligned); Y0 .. Y3: the C
+ * outputs (the others may be null).  Nothing but the outputs is written: the backward recomputes the logits. */
+int sslrec_mhcn_gate_fwd_f32(const float *X, int32_t N, int32_t d, const float *Wt, const float *B, int32_t C, float *Y0, float *Y1, float *Y2,
+                             float *Y3, void *stream);
+
+/* bytes of the backward's workspace: per gate and workgroup one [d, d] slab of dW^T and one [d] partial of db; 0 for a shape out of range */
+size_t sslrec_mhcn_gate_ws_bytes(int32_t N, int32_t d, int32_t C);
+
+/* From dY0 .. dY3 [N, d]: dX [N, d] = sum_c (dY_c (.) s_c + T_c W_c) with s_c the gate and T_c = dY_c (.) X (.) s_c (1 - s_c), dW [C, d, d]
+ * with dW[c] = T_c^T X in nn.Linear's out x in layout (NOT transposed), dB [C, d] the column sums of T_c.  All three are written. */
+int sslrec_mhcn_gate_bwd_f32(const float *X, int32_t N, int32_t d, const float *Wt, const float *B, int32_t C, const float *dY0, const float *dY1,
+                             const float *dY2, const float *dY3, float *dX, float *dW, float *dB, void *ws, void *stream);
+
+/* Workspace of the backward of the channel mix and of both directions of the loss: per-workgroup column partials and their total; 0 for
+ * a shape without a kernel. */
+size_t sslrec_mhcn_ws_bytes(int32_t N, int32_t d);
+
+/* Channel attention with the normalised layer sums, mhcn.py:54-64 as :81 and :112-113 call it, with :84-101:
+ *     weight_c = (attn * (embed_c @ attn_mat)).sum(1);  score = softmax over the three channels;  mixed = sum_c score_c embed_c
+ *     mixed_embed = mixed + simp_user_embeds / 2;       all_embeds_k += [F.normalize(embeds_k, p=2, dim=1)]
+ * v [d] = attn_mat @ attn^T is formed by the caller, weight_c = <embed_c, v>.  mixed [N, d] and scores [N, 3] are written; with
+ * a1 .. a4 (all four or none) also o_k = a_k + e_k / max(|e_k|, 1e-12) for e = (c1, c2, c3, simp), o_k may alias a_k. */
+int sslrec_mhcn_mix_fwd_f32(const float *c1, const float *c2, const float *c3, const float *simp, const float *v, int32_t N, int32_t d,
+                            const float *a1, const float *a2, const float *a3, const float *a4, float *mixed, float *scores, float *o1, float *o2,
+                            float *o3, float *o4, void *stream);
+
+/* Its backward from g_mixed [N, d] and, if given (all four or none), the gradients go_k of o_k: d1, d2, d3, dsimp [N, d] and dv [d] are
+ * written.  A row with |e_k| < 1e-12 receives go_k / 1e-12, the clamp's gradient.  scores: what the forward wrote.  The gradient in a_k
+ * is go_k itself and is not written. */
+int sslrec_mhcn_mix_bwd_f32(const float *c1, const float *c2, const float *c3, const float *simp, const float *v, const float *scores, int32_t N,
+                            int32_t d, const float *g_mixed, const float *go1, const float *go2, const float *go3, const float *go4, float *d1,
+                            float *d2, float *d3, float *dsimp, float *dv, void *ws, void *stream);
+
+/* The same sum for one table (the item side, mhcn.py:95-97): out = acc + x / max(|x|, 1e-12); dx from the gradient g of out. */
+int sslrec_mhcn_normadd_fwd_f32(const float *acc, const float *x, int32_t N, int32_t d, float *out, void *stream);
+int sslrec_mhcn_normadd_bwd_f32(const float *x, const float *g, int32_t N, int32_t d, float *dx, void *stream);
+
+/* Hierarchical mutual-information loss, mhcn.py:121-143 with edge = adj @ em formed by the caller:
+ *     pos = score(em, edge);  neg1 = score(row_shuffle(em), edge);  neg2 = score(row_col_shuffle(edge), em)
+ *     local = -((pos - neg1).sigmoid().log() + (neg1 - neg2).sigmoid().log()).sum()
+ *     graph = edge.mean(0);  global = -(score(edge, graph) - score(row_col_shuffle(edge), graph)).sigmoid().log().sum()
+ * The shuffles are given as int32 permutations: row_shuffle(x) = x[row_u], the two row_col_shuffle(x) = x[row_k][:, col_k] (k = 1 for
+ * neg2, k = 2 for the global term).  log sigmoid(x) is computed as min(x, 0) - log1p(exp(-|x|)): equal to the reference wherever that is
+ * finite, and finite where it returns -inf.  The loss is accumulated in double.  Written: loss [1], graph [d] and coef [N, 3], the three
+ * sigmoid(-x) per row, which the backward reads.  An index outside its range reads row / column 0: an undefined result, no error. */
+int sslrec_mhcn_ssl_fwd_f32(const float *em, const float *edge, const int32_t *row_u, const int32_t *col_1, const int32_t *row_1,
+                            const int32_t *col_2, const int32_t *row_2, int32_t N, int32_t d, float *coef, float *graph, float *loss, void *ws,
+                            void *stream);
+
+/* d_em, d_edge [N, d] (written) for the upstream gradient gloss [1] on the device.  inv_*: the inverse permutations (inv[p[i]] = i): every
+ * scatter through a permutation is a gather through its inverse.  No [N, d] shuffled copy exists in either direction. */
+int sslrec_mhcn_ssl_bwd_f32(const float *em, const float *edge, const int32_t *row_u, const int32_t *col_1, const int32_t *row_1,
+                            const int32_t *col_2, const int32_t *row_2, const int32_t *inv_row_u, const int32_t *inv_col_1,
+                            const int32_t *inv_row_1, const int32_t *inv_col_2, const int32_t *inv_row_2, const float *coef, const float *graph,
+                            const float *gloss, int32_t N, int32_t d, float *d_em, float *d_edge, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,16 @@ SIGNATURES = {
     'sslrec_pnn_bwd_f32': (C.c_int, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
     'sslrec_gt_scores_ws_bytes': (C.c_size_t, [_I, _I, _I]),
     'sslrec_gt_scores_f32': (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    'sslrec_mhcn_gate_fwd_f32': (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'sslrec_mhcn_gate_ws_bytes': (C.c_size_t, [_I, _I, _I]),
+    'sslrec_mhcn_gate_bwd_f32': (C.c_int, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_mhcn_ws_bytes': (C.c_size_t, [_I, _I]),
+    'sslrec_mhcn_mix_fwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_mhcn_mix_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_mhcn_normadd_fwd_f32': (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    'sslrec_mhcn_normadd_bwd_f32': (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    'sslrec_mhcn_ssl_fwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'sslrec_mhcn_ssl_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

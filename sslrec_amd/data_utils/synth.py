@@ -21,6 +21,16 @@ SHAPES = {
 }
 
 
+# social scenario: (users, items, train interactions, trust edges) -- the two bench shapes have the user / item counts of the
+# reference's yelp and epinions test pickles (its train and trust pickles are not shipped); the interaction and trust counts are chosen
+# so that the host builds the motif matrices of data_handler_social.py in well under a minute (their nnz: profiles/mhcn/)
+SOCIAL_SHAPES = {
+    'social-yelp': (43043, 66576, 400000, 400000),
+    'social-epinions': (18081, 251722, 300000, 250000),
+    'social-tiny': (150, 120, 900, 700),          # unit tests: all ten motifs occur, H_s and H_j have empty rows
+}
+
+
 def powerlaw_bipartite(n_user, n_item, n_edges, seed=2023, user_exp=2.0, item_exp=0.5,
                        max_user_frac=0.05):
     rng = np.random.default_rng(seed)
@@ -100,6 +110,74 @@ def community_bipartite(n_user, n_item, n_edges, n_comm=64, p_in=0.8, seed=2023,
 def make_dataset(name, seed=2023):
     n_user, n_item, n_edges = SHAPES[name]
     return powerlaw_bipartite(n_user, n_item, n_edges, seed)
+
+
+def uniform_bipartite(n_user, n_item, n_edges, seed=2023):
+    """`n_edges` distinct (user, item) pairs drawn uniformly: float64 ones in a COO matrix, entries in no particular order"""
+    rng = np.random.default_rng(seed)
+    keys = rng.choice(n_user * n_item, size=n_edges, replace=False).astype(np.int64)
+    return sp.coo_matrix((np.ones(n_edges, dtype=np.float64), ((keys // n_item).astype(np.int32), (keys % n_item).astype(np.int32))),
+                         shape=(n_user, n_item))
+
+
+def trust_graph(n_user, n_edges, reciprocal=0.3, n_isolated=None, seed=2023, comm_size=None, p_in=0.8):
+    """Seeded DIRECTED trust graph [n_user, n_user] as a COO matrix of float64 ones: no self loops, no duplicate entries, about
+    `reciprocal` of the entries have their reverse entry too, and `n_isolated` users (default: 1 in 30, at least 1) have no trust edge
+    in either direction.  Sources and targets are uniform over the other users; with `comm_size` the users with edges are dealt to
+    communities of that many and a pair lies inside one community with probability `p_in` (trust graphs are clustered: a uniform graph
+    of the bench sizes has next to no triangle, and MHCN's H_s is made of triangles).  `n_edges` is met to within rounding."""
+    rng = np.random.default_rng(seed)
+    if n_isolated is None:
+        n_isolated = max(1, n_user // 30)
+    active = np.sort(rng.permutation(n_user)[:n_user - n_isolated]).astype(np.int64)
+    m = active.size
+    if m < 2:
+        raise ValueError('trust_graph: fewer than two users with trust edges')
+    n_pairs = int(round(n_edges * reciprocal / 2.0))            # unordered pairs that get both directions
+    n_single = max(0, n_edges - 2 * n_pairs)
+    want = n_pairs + n_single
+    if want > m * (m - 1) // 2:
+        raise ValueError('trust_graph: %d edges do not fit %d users' % (n_edges, m))
+    keys = np.empty(0, dtype=np.int64)                          # distinct unordered pairs lo < hi as lo * m + hi
+    rounds = 0
+    while keys.size < want and rounds < 64:
+        a = rng.integers(0, m, size=2 * (want - keys.size) + 16)
+        b = rng.integers(0, m, size=a.size)
+        if comm_size is not None:
+            start = (a // comm_size) * comm_size
+            inside = start + rng.integers(0, comm_size, size=a.size)
+            b = np.where((rng.random(a.size) < p_in) & (inside < m), inside, b)
+        ok = a != b
+        lo, hi = np.minimum(a, b)[ok], np.maximum(a, b)[ok]
+        keys = np.unique(np.concatenate([keys, lo * m + hi]))
+        rounds += 1
+    if keys.size < want:
+        raise RuntimeError('could not reach the requested number of trust edges')
+    keys = rng.permutation(keys)[:want]
+    lo, hi = active[keys // m], active[keys % m]
+    flip = rng.random(want) < 0.5                               # direction of the one-way edges
+    src = np.where(flip, hi, lo)
+    dst = np.where(flip, lo, hi)
+    rows = np.concatenate([src, dst[:n_pairs]])                 # the first n_pairs pairs are reciprocated
+    cols = np.concatenate([dst, src[:n_pairs]])
+    order = rng.permutation(rows.size)
+    return sp.coo_matrix((np.ones(rows.size, dtype=np.float64), (rows[order].astype(np.int32), cols[order].astype(np.int32))),
+                         shape=(n_user, n_user))
+
+
+def make_social_dataset(name, seed=2023):
+    """(trn_mat, trust_mat) of SOCIAL_SHAPES[name]: power-law interactions for the bench shapes, uniform ones for social-tiny (whose
+    motif counts the tests pin), and a trust graph with 30 % reciprocated entries"""
+    n_user, n_item, n_edges, n_trust = SOCIAL_SHAPES[name]
+    if name == 'social-tiny':
+        trn = uniform_bipartite(n_user, n_item, n_edges, seed)
+        # (seed + 19: at the default seed 2023 the graph then holds all ten motifs, the fully reciprocated triangle among them -- about
+        # one graph in three of this size does; tests/test_mhcn_host.py asserts it)
+        trust = trust_graph(n_user, n_trust, 0.3, 5, seed + 19)
+    else:
+        trn = powerlaw_bipartite(n_user, n_item, n_edges, seed)
+        trust = trust_graph(n_user, n_trust, 0.3, None, seed + 17, comm_size=40)
+    return trn, trust
 
 
 def split_holdout(trn_mat, frac, seed):

@@ -2661,6 +2661,293 @@ def sum_squares(x, weight=1.0):
 
 
 # ----------------------------------------------------------------------------------------------
+# MHCN (reference models/social/mhcn.py): self-gating, channel attention with the normalised layer sums, hierarchical
+# mutual-information loss.  csrc/mhcn.hip holds the row-wise kernels of the last two; the composed torch expressions below take any
+# dtype and device, run where no kernel exists (embedding sizes outside MHCN_DIMS, CPU tensors, float64) and are what the kernels are
+# measured against (SSLREC_MHCN_FUSED=0).
+# ----------------------------------------------------------------------------------------------
+MHCN_DIMS = (32, 64, 128)
+MHCN_FUSED = os.environ.get('SSLREC_MHCN_FUSED', '1') != '0'      # 0: the composed torch expressions at every size (measurement)
+MHCN_NORM_EPS = 1e-12                                             # F.normalize's clamp of the norm
+
+
+def mhcn_fused_ok(d):
+    """embedding sizes csrc/mhcn.hip has kernels for"""
+    return int(d) in MHCN_DIMS
+
+
+def _mhcn_kernel_path(*tensors):
+    x = tensors[0]
+    return (MHCN_FUSED and x.is_cuda and x.dim() == 2 and mhcn_fused_ok(x.shape[1]) and 1 <= x.shape[0] < 2 ** 31 - 1
+            and all(t.is_cuda and t.dtype == torch.float32 for t in tensors))
+
+
+def _mhcn_table(t):
+    """fp32, contiguous, 16-byte aligned (rows are read as float4)"""
+    t = _f32c(t)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _mhcn_ws(N, d, device):
+    return torch.empty(_lib.load().sslrec_mhcn_ws_bytes(int(N), int(d)) // 4 + 1, dtype=torch.float32, device=device)
+
+
+def _self_gate_composed(x, weights, biases):
+    return tuple(x * torch.sigmoid(torch.nn.functional.linear(x, w, b)) for w, b in zip(weights, biases))
+
+
+class _SelfGateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, *wb):
+        n_gates = len(wb) // 2
+        x = _mhcn_table(x)
+        N, d = x.shape
+        # one stacked copy of the C small tensors, the weights transposed: C d (d + 1) floats
+        wt = torch.stack([w.t() for w in wb[:n_gates]]).to(torch.float32).contiguous()
+        b = torch.stack(list(wb[n_gates:])).to(torch.float32).contiguous()
+        ys = [torch.empty(N, d, dtype=torch.float32, device=x.device) for _ in range(n_gates)]
+        rc = _lib.load().sslrec_mhcn_gate_fwd_f32(x.data_ptr(), N, d, wt.data_ptr(), b.data_ptr(), n_gates,
+                                                  *([y.data_ptr() for y in ys] + [None] * (4 - n_gates)), _stream())
+        _lib.check(rc, 'sslrec_mhcn_gate_fwd_f32')
+        ctx.save_for_backward(x, wt, b)          # (the inputs only: the backward recomputes the logits)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *gys):
+        x, wt, b = ctx.saved_tensors
+        n_gates = wt.shape[0]
+        N, d = x.shape
+        gys = [_mhcn_table(g) for g in gys]
+        lib = _lib.load()
+        dx = torch.empty_like(x)
+        dw = torch.empty(n_gates, d, d, dtype=torch.float32, device=x.device)
+        db = torch.empty(n_gates, d, dtype=torch.float32, device=x.device)
+        ws = torch.empty(lib.sslrec_mhcn_gate_ws_bytes(N, d, n_gates) // 4 + 1, dtype=torch.float32, device=x.device)
+        rc = lib.sslrec_mhcn_gate_bwd_f32(x.data_ptr(), N, d, wt.data_ptr(), b.data_ptr(), n_gates,
+                                          *([g.data_ptr() for g in gys] + [None] * (4 - n_gates)), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                          ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_mhcn_gate_bwd_f32')
+        return (dx, *dw.unbind(0), *db.unbind(0))
+
+
+def self_gate(x, weights, biases):
+    """(Y_1, ..., Y_C), Y_c = x * sigmoid(x @ W_c^T + b_c): the self-gating units of mhcn.py:34-52 for C <= 4 gates that share one
+    x [N, d].  weights / biases: those of C nn.Linear(d, d) (out x in layout).  Differentiable in x, every W_c and every b_c.
+
+    One forward launch reads x and writes the C tables, the products on the exact-fp32 MFMA (csrc/mhcn_gate.hip); the backward recomputes
+    the logits, so no [N, d] pre-activation or gate tensor is kept, and sums dW_c and db_c from per-workgroup slabs in a fixed order:
+    no float atomics, two calls give the same bits.  fp32 HIP tensors with d in {32, 64, 128} run the kernels (mhcn_fused_ok);
+    everything else, and SSLREC_MHCN_FUSED=0, the composed torch expression."""
+    weights, biases = tuple(weights), tuple(biases)
+    if not 1 <= len(weights) <= 4 or len(weights) != len(biases):
+        raise ValueError('self_gate: 1 to 4 gates with one bias each expected, got %d and %d' % (len(weights), len(biases)))
+    if x.dim() != 2:
+        raise ValueError('self_gate: x [N, d] expected, got %s' % (tuple(x.shape),))
+    d = x.shape[1]
+    for w, b in zip(weights, biases):
+        if tuple(w.shape) != (d, d) or tuple(b.shape) != (d,):
+            raise ValueError('self_gate: weights [d, d] and biases [d] expected for d = %d, got %s and %s' % (d, tuple(w.shape), tuple(b.shape)))
+    if _mhcn_kernel_path(x, *weights, *biases):
+        return _SelfGateFn.apply(x, *weights, *biases)
+    return _self_gate_composed(x, weights, biases)
+
+
+def _channel_mix_composed(c1, c2, c3, simp, v, sums=None):
+    """(mixed, scores, sums_out) in torch: weight_c = <e_c, v>, softmax over the channels, mixed = sum_c s_c e_c + simp / 2"""
+    chans = (c1, c2, c3)
+    scores = torch.softmax(torch.stack([e @ v for e in chans], dim=1), dim=-1)
+    mixed = simp / 2
+    for i, e in enumerate(chans):
+        mixed = mixed + scores[:, i:i + 1] * e
+    outs = None
+    if sums is not None:
+        outs = tuple(a + torch.nn.functional.normalize(e, p=2, dim=1, eps=MHCN_NORM_EPS) for a, e in zip(sums, (c1, c2, c3, simp)))
+    return mixed, scores, outs
+
+
+class _ChannelMixFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, c1, c2, c3, simp, v, *sums):
+        tabs = [_mhcn_table(x) for x in (c1, c2, c3, simp)]
+        v = _mhcn_table(v)
+        accs = [_mhcn_table(a) for a in sums]
+        N, d = tabs[0].shape
+        dev = tabs[0].device
+        mixed = torch.empty(N, d, dtype=torch.float32, device=dev)
+        scores = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        outs = [torch.empty(N, d, dtype=torch.float32, device=dev) for _ in accs]
+        rc = _lib.load().sslrec_mhcn_mix_fwd_f32(*[x.data_ptr() for x in tabs], v.data_ptr(), N, d, *([a.data_ptr() for a in accs] or [None] * 4),
+                                                 mixed.data_ptr(), scores.data_ptr(), *([o.data_ptr() for o in outs] or [None] * 4), _stream())
+        _lib.check(rc, 'sslrec_mhcn_mix_fwd_f32')
+        ctx.save_for_backward(*tabs, v, scores)
+        ctx.with_sums = bool(accs)
+        ctx.mark_non_differentiable(scores)
+        return (mixed, scores, *outs)
+
+    @staticmethod
+    def backward(ctx, g_mixed, _g_scores, *g_outs):
+        *tabs, v, scores = ctx.saved_tensors
+        N, d = tabs[0].shape
+        dev = tabs[0].device
+        g_mixed = _mhcn_table(g_mixed)
+        gos = [_mhcn_table(g) for g in g_outs] if ctx.with_sums else []
+        ds = [torch.empty(N, d, dtype=torch.float32, device=dev) for _ in range(4)]
+        dv = torch.empty(d, dtype=torch.float32, device=dev)
+        ws = _mhcn_ws(N, d, dev)
+        rc = _lib.load().sslrec_mhcn_mix_bwd_f32(*[x.data_ptr() for x in tabs], v.data_ptr(), scores.data_ptr(), N, d, g_mixed.data_ptr(),
+                                                 *([g.data_ptr() for g in gos] or [None] * 4), *[x.data_ptr() for x in ds], dv.data_ptr(),
+                                                 ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_mhcn_mix_bwd_f32')
+        return (*ds, dv, *gos)
+
+
+def channel_mix(c1, c2, c3, simp, v, sums=None, return_scores=False):
+    """mixed [N, d] = sum_c s_c e_c + simp / 2 with s = softmax_c(<e_c, v>) per row: `_channel_attention(c1, c2, c3)[0] + simp / 2` of
+    mhcn.py:54-64, :81, :112-113.  v [d] = attn_mat @ attn.T is formed by the caller (the reference's (attn * (e @ attn_mat)).sum(1) with
+    the product commuted), so autograd carries dv to both parameters.
+
+    sums = (a1, a2, a3, a4): the same launch also returns (a_k + F.normalize(e_k, p=2, dim=1, eps=1e-12))_k for e = (c1, c2, c3, simp),
+    the layer sums of :84-101, so the four raw tables are read once.  The clamp of the norm is a clamp: a zero row gives zeros forward
+    and g / 1e-12 backward.  return_scores=True appends the [N, 3] scores the reference's `_channel_attention` returns; through the
+    kernels they carry no gradient (the model uses them for nothing).
+
+    Returns mixed | (mixed, sums_out) | (mixed, scores) | (mixed, sums_out, scores).  Differentiable in the four tables, v and the four
+    sums; backward is one launch over the rows plus the ordered finish for dv; no float atomics, two calls give the same bits.
+    fp32 HIP tensors with d in {32, 64, 128} run csrc/mhcn.hip (mhcn_fused_ok); everything else, and SSLREC_MHCN_FUSED=0, the composed
+    torch expression."""
+    tabs = (c1, c2, c3, simp)
+    if any(x.dim() != 2 or x.shape != c1.shape for x in tabs) or v.dim() != 1 or v.shape[0] != c1.shape[1]:
+        raise ValueError('channel_mix: four [N, d] tables and v [d] expected, got %s and %s' % ([tuple(x.shape) for x in tabs], tuple(v.shape)))
+    if sums is not None:
+        sums = tuple(sums)
+        if len(sums) != 4 or any(a.shape != c1.shape for a in sums):
+            raise ValueError('channel_mix: sums must be four tables of the shape of the channels')
+    if _mhcn_kernel_path(*tabs, v, *(sums or ())):
+        res = _ChannelMixFn.apply(*tabs, v, *(sums or ()))
+        mixed, scores, outs = res[0], res[1], (tuple(res[2:]) if sums is not None else None)
+    else:
+        mixed, scores, outs = _channel_mix_composed(*tabs, v, sums)
+    ret = (mixed,) + ((outs,) if sums is not None else ()) + ((scores,) if return_scores else ())
+    return ret[0] if len(ret) == 1 else ret
+
+
+def _normalize_add_composed(acc, y):
+    return acc + torch.nn.functional.normalize(y, p=2, dim=1, eps=MHCN_NORM_EPS)
+
+
+class _NormalizeAddFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, acc, y):
+        acc, y = _mhcn_table(acc), _mhcn_table(y)
+        N, d = y.shape
+        out = torch.empty_like(y)
+        _lib.check(_lib.load().sslrec_mhcn_normadd_fwd_f32(acc.data_ptr(), y.data_ptr(), N, d, out.data_ptr(), _stream()), 'sslrec_mhcn_normadd_fwd_f32')
+        ctx.save_for_backward(y)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        g = _mhcn_table(g)
+        dy = None
+        if ctx.needs_input_grad[1]:
+            dy = torch.empty_like(y)
+            _lib.check(_lib.load().sslrec_mhcn_normadd_bwd_f32(y.data_ptr(), g.data_ptr(), y.shape[0], y.shape[1], dy.data_ptr(), _stream()),
+                       'sslrec_mhcn_normadd_bwd_f32')
+        return g, dy
+
+
+def normalize_add(acc, y):
+    """acc + F.normalize(y, p=2, dim=1, eps=1e-12) for one table (the item side, mhcn.py:95-97) as one launch, forward and backward;
+    semantics, shapes and the composed path as channel_mix"""
+    if acc.shape != y.shape or y.dim() != 2:
+        raise ValueError('normalize_add: two [N, d] tables expected, got %s and %s' % (tuple(acc.shape), tuple(y.shape)))
+    if _mhcn_kernel_path(y, acc):
+        return _NormalizeAddFn.apply(acc, y)
+    return _normalize_add_composed(acc, y)
+
+
+def log_sigmoid_stable(x):
+    """log sigmoid(x) = min(x, 0) - log1p(exp(-|x|)), finite for every finite x"""
+    return torch.clamp(x, max=0) - torch.log1p(torch.exp(-x.abs()))
+
+
+def _hier_ssl_composed(em, edge, perms):
+    row_u, col_1, row_1, col_2, row_2 = [p.long() for p in perms]
+    pos = (em * edge).sum(1)
+    neg1 = (em[row_u] * edge).sum(1)
+    neg2 = (edge[row_1][:, col_1] * em).sum(1)
+    local_ssl = -(log_sigmoid_stable(pos - neg1) + log_sigmoid_stable(neg1 - neg2)).sum()
+    graph = edge.mean(0)
+    pos = (edge * graph).sum(1)
+    neg1 = (edge[row_2][:, col_2] * graph).sum(1)
+    global_ssl = -log_sigmoid_stable(pos - neg1).sum()
+    return local_ssl + global_ssl
+
+
+def _inverse_perm(p):
+    inv = torch.empty_like(p)
+    inv[p.long()] = torch.arange(p.numel(), dtype=p.dtype, device=p.device)
+    return inv
+
+
+class _HierSslFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, em, edge, *perms):
+        em, edge = _mhcn_table(em), _mhcn_table(edge)
+        N, d = em.shape
+        dev = em.device
+        coef = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        graph = torch.empty(d, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _mhcn_ws(N, d, dev)
+        rc = _lib.load().sslrec_mhcn_ssl_fwd_f32(em.data_ptr(), edge.data_ptr(), *[p.data_ptr() for p in perms], N, d, coef.data_ptr(),
+                                                 graph.data_ptr(), loss.data_ptr(), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_mhcn_ssl_fwd_f32')
+        ctx.save_for_backward(em, edge, coef, graph, *perms)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        em, edge, coef, graph, *perms = ctx.saved_tensors
+        N, d = em.shape
+        dev = em.device
+        invs = [_inverse_perm(p) for p in perms]          # once per call: a scatter through p is a gather through its inverse
+        g = g.reshape(1).to(torch.float32).contiguous()
+        d_em = torch.empty(N, d, dtype=torch.float32, device=dev)
+        d_edge = torch.empty(N, d, dtype=torch.float32, device=dev)
+        ws = _mhcn_ws(N, d, dev)
+        rc = _lib.load().sslrec_mhcn_ssl_bwd_f32(em.data_ptr(), edge.data_ptr(), *[p.data_ptr() for p in perms], *[p.data_ptr() for p in invs],
+                                                 coef.data_ptr(), graph.data_ptr(), g.data_ptr(), N, d, d_em.data_ptr(), d_edge.data_ptr(),
+                                                 ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_mhcn_ssl_bwd_f32')
+        return (d_em, d_edge) + (None,) * len(perms)
+
+
+def hier_ssl_loss(em, edge, perms):
+    """The scalar of `_hierarchical_self_supervision` (mhcn.py:121-143) from em [N, d], edge = H @ em (the caller's SpMM, whose backward is
+    the existing one) and the five permutations perms = (row_u, col_1, row_1, col_2, row_2) as index tensors: row_shuffle(x) = x[row_u],
+    the row_col_shuffle of neg2 = x[row_1][:, col_1], that of the global term = x[row_2][:, col_2] (t.t(t.t(x)[c])[r] equals x[r][:, c]).
+
+    log sigmoid(x) is computed as min(x, 0) - log1p(exp(-|x|)).  This equals the reference's `sigmoid().log()` wherever that is finite
+    and stays finite where the reference returns -inf (arguments below about -104 in float32).  The loss is accumulated in double.
+    Differentiable in em and edge; the permutations must be permutations (on the kernel path an index outside its range gives an
+    undefined result, never an access outside the tables; a repeated index gives the forward of that index list and a backward that is
+    not its gradient).  No [N, d] shuffled copy is made in either direction, no float atomics, two calls give the same bits.  fp32 HIP
+    tensors with d in {32, 64, 128} run csrc/mhcn.hip; everything else, and SSLREC_MHCN_FUSED=0, the composed torch expression."""
+    perms = tuple(perms)
+    if em.dim() != 2 or edge.shape != em.shape or len(perms) != 5:
+        raise ValueError('hier_ssl_loss: em and edge [N, d] and five permutations expected')
+    N, d = em.shape
+    for p, n in zip(perms, (N, d, N, d, N)):
+        if p.dim() != 1 or p.numel() != n or p.dtype not in (torch.int32, torch.int64):
+            raise ValueError('hier_ssl_loss: the permutations (row_u, col_1, row_1, col_2, row_2) have %d, %d, %d, %d, %d integer entries' % (N, d, N, d, N))
+    if _mhcn_kernel_path(em, edge):
+        return _HierSslFn.apply(em, edge, *[p.to(device=em.device, dtype=torch.int32).contiguous() for p in perms])
+    return _hier_ssl_composed(em, edge, [p.to(em.device) for p in perms])
+
+
+# ----------------------------------------------------------------------------------------------
 # all-rank evaluation and negative sampling on the device (SURVEY.md §8f ranks 2 and 3)
 # ----------------------------------------------------------------------------------------------
 def full_predict(user_table, item_table, users, train_mask=None):

@@ -1019,6 +1019,53 @@ int sslrec_mhcn_ssl_bwd_f32(const float *em, const float *edge, const int32_t *r
                             const int32_t *inv_row_1, const int32_t *inv_col_2, const int32_t *inv_row_2, const float *coef, const float *graph,
                             const float *gloss, int32_t N, int32_t d, float *d_em, float *d_edge, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * KGIN's kernels (csrc/kgin.hip), models/kg/kgin.py.  Tables are [*, d] fp32 row-major, 16-byte aligned, d in {32, 64, 128}.  No float
+ * atomics; two calls give the same bits.  SSLREC_E_BADARG before any launch for a null pointer, a misaligned table or a shape outside
+ * these ranges.
+ *
+ * An EDGE LIST in some order (graph.RelGraph builds one by head, one by tail and one by relation): ptr [n_dest + 1] int32 and per slot
+ * ia, ib (the rows of the two tables that the slot multiplies) and eid (the edge's id in the caller's numbering: keep [E] uint8, or
+ * null, is read through it).  A destination of more than SSLREC_KGIN_CHUNK slots is LONG: chunk_dest / chunk_begin [n_chunks] list its
+ * chunks (all chunks of one destination in a row, in slot order), long_dest [n_long] / long_ptr [n_long + 1] its range of chunks;
+ * part [n_chunks, d] (and part_cnt [n_chunks] int32 forward) take the chunks' sums, which a second launch adds in chunk order.  The
+ * index arrays must hold valid rows: the kernels do not check them.
+ *
+ * Relational aggregation, kgin.py:33-36:
+ *     edge_relation_emb = weight[edge_type - 1];  neigh_relation_emb = entity_emb[tail] * edge_relation_emb
+ *     entity_agg = scatter_mean(src=neigh_relation_emb, index=head, dim_size=n_entities, dim=0)
+ * on the list ordered by head (ia = tail, ib = relation): Y [n_dest, d] and cnt [n_dest], the integer number of kept edges of every head
+ * (the mean of no edge is 0).  W [R, d] sits in LDS when it fits 48 KiB. */
+#define SSLREC_KGIN_CHUNK 512
+int sslrec_kgin_rel_fwd_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                            const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                            const int32_t *long_ptr, int32_t n_long, const float *X, const float *W, int32_t R, int32_t d, const uint8_t *keep,
+                            int32_t *cnt, float *Y, float *part, int32_t *part_cnt, void *stream);
+
+/* The backward of the same lines, one call per gradient: out[dest] = sum over the kept slots of G[ia] (.) B[ib] / max(cnt[ia], 1) with
+ * ia = head in both.  dX: the list ordered by tail, B = W [R, d] (b_in_lds = 1: staged in LDS when it fits), ib = relation.
+ * dW: the list ordered by relation, B = X, ib = tail (b_in_lds = 0).  cnt: what the forward wrote. */
+int sslrec_kgin_rel_bwd_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                            const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                            const int32_t *long_ptr, int32_t n_long, const float *G, const float *B, int32_t n_b_rows, int32_t b_in_lds, int32_t d,
+                            const uint8_t *keep, const int32_t *cnt, float *out, float *part, void *stream);
+
+/* Factor modulation of the user side, kgin.py:38-46:
+ *     score = softmax(user_emb @ latent_emb.t(), dim=1);  disen_weight = softmax(disen_weight_att, -1) @ weight
+ *     user_agg = user_agg * (disen_weight.expand(U, F, d) * score.unsqueeze(-1)).sum(dim=1) + user_agg
+ * out = agg (.) (p @ Dm) + agg per row with p = softmax_f <u, latent_f>; latent, Dm [F, d], 1 <= F <= 8, Dm = disen_weight formed by the
+ * caller.  One launch, no [U, F, d] tensor. */
+int sslrec_kgin_fm_fwd_f32(const float *agg, const float *u, const float *latent, const float *Dm, int32_t U, int32_t d, int32_t F, float *out,
+                           void *stream);
+
+/* bytes of the backward's workspace (per workgroup one [2 F, d] slab); 0 for a shape without a kernel */
+size_t sslrec_kgin_fm_ws_bytes(int32_t U, int32_t d, int32_t F);
+
+/* Its backward from gout [U, d]: d_agg, d_u [U, d] and d_latent_and_d [2 F, d] (dlatent, then dDm) are written; the softmax is
+ * recomputed, the two [F, d] sums over rows come from per-workgroup slabs added in a fixed order by a finishing launch. */
+int sslrec_kgin_fm_bwd_f32(const float *agg, const float *u, const float *latent, const float *Dm, const float *gout, int32_t U, int32_t d, int32_t F,
+                           float *d_agg, float *d_u, float *d_latent_and_d, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

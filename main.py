@@ -4,9 +4,11 @@
     python main.py --model lightgcn [--dataset yelp|gowalla|amazon] [--device cuda] [--cuda 0]
                    [--synthetic amazon-book|yelp|gowalla|tiny]
     python main.py --model mhcn [--dataset ciao|epinions|yelp|lastfm] [--synthetic social-yelp|social-epinions|social-tiny]
+    python main.py --model kgin [--dataset mind|alibaba-fashion|last-fm] [--synthetic kg-last-fm|kg-alibaba|kg-tiny]
 
 Datasets are read from `./datasets/general_cf/sparse_*/{train,valid,test}_mat.pkl` (social models:
-`./datasets/social/*/{trn,tst,trust}_mat.pkl`) relative to the working directory, exactly like
+`./datasets/social/*/{trn,tst,trust}_mat.pkl`; kg models: `./datasets/kg/*_kg/{train,test,kg_final}.txt`)
+relative to the working directory, exactly like
 upstream; `--synthetic` (an addition) generates a seeded graph of a BASELINE shape instead, for
 machines without the pickles."""
 import sys

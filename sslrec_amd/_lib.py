@@ -218,6 +218,11 @@ SIGNATURES = {
     'sslrec_mhcn_normadd_bwd_f32': (C.c_int, [_P, _P, _I, _I, _P, _P]),
     'sslrec_mhcn_ssl_fwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     'sslrec_mhcn_ssl_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    'sslrec_kgin_rel_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'sslrec_kgin_rel_bwd_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'sslrec_kgin_fm_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    'sslrec_kgin_fm_ws_bytes': (C.c_size_t, [_I, _I, _I]),
+    'sslrec_kgin_fm_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

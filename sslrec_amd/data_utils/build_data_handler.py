@@ -1,5 +1,5 @@
 """Reflection factory: data handler class chosen from configs['data']['type']
-(reference data_utils/build_data_handler.py:4-14): general_cf and social (MHCN) exist."""
+(reference data_utils/build_data_handler.py:4-14): general_cf, social (MHCN) and kg (KGIN) exist."""
 import importlib
 import importlib.util
 

@@ -31,6 +31,16 @@ SOCIAL_SHAPES = {
 }
 
 
+# kg scenario: (users, items, entities incl. items, canonical relations, train interactions, canonical triplets) -- the two bench
+# shapes have the counts of the reference's last-fm and alibaba-fashion knowledge graphs (KGIN paper, table 1); the handler doubles the
+# triplets with their inverses and adds the interact relation
+KG_SHAPES = {
+    'kg-last-fm': (23566, 48123, 106389, 9, 3034796, 464567),
+    'kg-alibaba': (114737, 30040, 89196, 51, 1781093, 279155),
+    'kg-tiny': (60, 50, 90, 4, 400, 300),          # unit tests: an entity without edges, a pair under two relations, a relation that occurs once
+}
+
+
 def powerlaw_bipartite(n_user, n_item, n_edges, seed=2023, user_exp=2.0, item_exp=0.5,
                        max_user_frac=0.05):
     rng = np.random.default_rng(seed)
@@ -178,6 +188,61 @@ def make_social_dataset(name, seed=2023):
         trn = powerlaw_bipartite(n_user, n_item, n_edges, seed)
         trust = trust_graph(n_user, n_trust, 0.3, None, seed + 17, comm_size=40)
     return trn, trust
+
+
+def kg_triplets(n_item, n_entity, n_rel, n_triplets, seed=2023, tail_exp=1.0, p_item_head=0.85):
+    """`n_triplets` distinct canonical triplets (head, relation, tail) as an int32 [T, 3] array in np.unique's row order -- what
+    np.unique(np.loadtxt('kg_final.txt'), axis=0) yields.  Entities [0, n_item) are the items, the others attributes.  Heads are items
+    (`p_item_head`) or attributes, tails are attributes drawn by a Zipf law of exponent `tail_exp`, so a few attribute entities are hubs with
+    a large share of all edges.  By construction: the attribute n_item + (n_entity - n_item) // 2 occurs in no triplet, one (head, tail)
+    pair occurs under two relations, relation n_rel - 1 occurs exactly once (with tail n_entity - 1, so both maxima are present)."""
+    if n_rel < 3 or n_entity - n_item < 4 or n_triplets < 3:
+        raise ValueError('kg_triplets: at least 3 relations, 4 attribute entities and 3 triplets')
+    rng = np.random.default_rng(seed)
+    n_attr = n_entity - n_item
+    isolated = n_item + n_attr // 2
+    w = 1.0 / np.power(np.arange(1, n_attr + 1, dtype=np.float64), tail_exp)
+    cdf = np.cumsum(w / w.sum())
+    attr_of_rank = n_item + rng.permutation(n_attr)
+    rel_w = 1.0 / np.arange(1, n_rel, dtype=np.float64)             # relations 0 .. n_rel - 2, skewed
+    rel_cdf = np.cumsum(rel_w / rel_w.sum())
+    need = n_triplets - 2
+    keys = np.empty(0, dtype=np.int64)                              # (h * n_rel + r) * n_entity + t
+    rounds = 0
+    while keys.size < need and rounds < 64:
+        m = 2 * (need - keys.size) + 64
+        h = np.where(rng.random(m) < p_item_head, rng.integers(0, n_item, m), n_item + rng.integers(0, n_attr, m)).astype(np.int64)
+        t = attr_of_rank[np.minimum(np.searchsorted(cdf, rng.random(m), side='right'), n_attr - 1)].astype(np.int64)
+        r = np.minimum(np.searchsorted(rel_cdf, rng.random(m), side='right'), n_rel - 2).astype(np.int64)
+        ok = (h != t) & (h != isolated) & (t != isolated)
+        keys = np.unique(np.concatenate([keys, ((h * n_rel + r) * n_entity + t)[ok]]))
+        rounds += 1
+    if keys.size < need:
+        raise RuntimeError('could not reach the requested number of triplets')
+    if keys.size > need:
+        keys = rng.choice(keys, size=need, replace=False)
+    have = set(keys.tolist())
+    h0, r0, t0 = int(keys[0] // n_entity // n_rel), int(keys[0] // n_entity % n_rel), int(keys[0] % n_entity)
+    twin = next(k for k in (((h0 * n_rel + (r0 + s) % (n_rel - 1)) * n_entity + t0) for s in range(1, n_rel - 1)) if k not in have)
+    rare = ((n_item - 1) * n_rel + (n_rel - 1)) * n_entity + (n_entity - 1)
+    keys = np.concatenate([keys, np.array([twin, rare], dtype=np.int64)])
+    trip = np.stack([keys // n_entity // n_rel, keys // n_entity % n_rel, keys % n_entity], axis=1).astype(np.int32)
+    return np.unique(trip, axis=0)
+
+
+def make_kg_dataset(name, seed=2023, test_frac=None):
+    """(train_cf [n, 2], test_cf [m, 2], canonical triplets [T, 3]) of KG_SHAPES[name]: the (user, item) pairs in the order the
+    reference's `_read_cf` yields them from train.txt / test.txt (by user; the items of a user in ascending order) and what
+    np.unique(np.loadtxt(kg_final.txt), axis=0) yields.  Power-law interactions for the bench shapes, uniform ones for kg-tiny."""
+    n_user, n_item, n_entity, n_rel, n_inter, n_trip = KG_SHAPES[name]
+    tiny = name == 'kg-tiny'
+    trn = uniform_bipartite(n_user, n_item, n_inter, seed) if tiny else powerlaw_bipartite(n_user, n_item, n_inter, seed)
+    tst = split_holdout(trn, test_frac if test_frac is not None else (0.05 if tiny else 0.002), seed + 2)
+
+    def pairs(m):
+        order = np.lexsort((m.col, m.row))
+        return np.stack([m.row[order], m.col[order]], axis=1).astype(np.int64)
+    return pairs(trn), pairs(tst), kg_triplets(n_item, n_entity, n_rel, n_trip, seed + 23)
 
 
 def split_holdout(trn_mat, frac, seed):

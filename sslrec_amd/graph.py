@@ -705,6 +705,84 @@ class EdgePattern:
         return cls(idx[0], idx[1], adj.shape[0])
 
 
+REL_CHUNK = 512        # SSLREC_KGIN_CHUNK of include/sslrec_hip.h
+
+
+class RelEdgeList:
+    """The typed edges of a RelGraph in one ORDER, as csrc/kgin.hip walks them: `ptr` [n_dest + 1], and per slot `ia` / `ib` (the rows of
+    the two tables the slot multiplies) and `eid` (the edge's id in the caller's order), all int32 on `device`.  Slots of one destination
+    keep the caller's edge order (a stable sort).  A destination of more than REL_CHUNK slots is long: `chunk_dest` / `chunk_begin`
+    [n_chunks] list its chunks of REL_CHUNK slots, `long_dest` [n_long] / `long_ptr` [n_long + 1] the range of chunks of each."""
+
+    def __init__(self, dest, ia, ib, n_dest, device):
+        dest = np.asarray(dest, dtype=np.int64)
+        order = np.argsort(dest, kind='stable')
+        deg = np.bincount(dest, minlength=n_dest).astype(np.int64)
+        ptr = np.concatenate([[0], np.cumsum(deg)])
+        long_dest = np.nonzero(deg > REL_CHUNK)[0]
+        n_ch = (deg[long_dest] + REL_CHUNK - 1) // REL_CHUNK
+        long_ptr = np.concatenate([[0], np.cumsum(n_ch)])
+        chunk_dest = np.repeat(long_dest, n_ch)
+        chunk_begin = ptr[chunk_dest] + (np.arange(chunk_dest.size) - np.repeat(long_ptr[:-1], n_ch)) * REL_CHUNK
+        self.n_dest, self.n_slots = int(n_dest), int(dest.size)
+        self.n_chunks, self.n_long = int(chunk_dest.size), int(long_dest.size)
+        self.max_len = int(deg.max()) if deg.size else 0
+
+        def dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+        self.ptr, self.eid = dev(ptr), dev(order)
+        self.ia, self.ib = dev(np.asarray(ia)[order]), dev(np.asarray(ib)[order])
+        self.chunk_dest, self.chunk_begin = dev(chunk_dest), dev(chunk_begin)
+        self.long_dest, self.long_ptr = dev(long_dest), dev(long_ptr)
+
+    def c_args(self):
+        """the leading arguments of sslrec_kgin_rel_{fwd,bwd}_f32"""
+        p = lambda t: t.data_ptr() if t.numel() else None
+        return (self.ptr.data_ptr(), p(self.ia), p(self.ib), p(self.eid), self.n_dest, self.n_slots, p(self.chunk_dest), p(self.chunk_begin),
+                self.n_chunks, p(self.long_dest), self.long_ptr.data_ptr() if self.n_long else None, self.n_long)
+
+
+class RelGraph:
+    """A relation-typed directed graph for ops.rel_aggregate: E edges (head_e, tail_e, rel_e) over N entities and R relations, rel_e in
+    [0, R).  Unlike EdgePattern the same (head, tail) pair may occur several times (under several relations, or even the same one): every
+    edge counts.  Built ONCE on the host with numpy from the edges in the caller's order, which is the numbering of the keep masks; a
+    per-step edge sample rebuilds nothing, the kernels read the mask through the edge ids.  Holds
+
+      by_head  ordered by head:      ia = tail, ib = relation     (the forward)
+      by_tail  ordered by tail:      ia = head, ib = relation     (dX)
+      by_rel   ordered by relation:  ia = head, ib = tail         (dW)
+
+    as RelEdgeList (int32 on `device`; only when `device` is a HIP device), and `head`, `tail`, `rel` int64 [E] in the caller's order on
+    `device` for the composed torch form."""
+
+    def __init__(self, head, tail, rel, n, n_rel, device='cpu'):
+        head, tail, rel = (np.asarray(torch.as_tensor(a).cpu().numpy() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in (head, tail, rel))
+        n, n_rel = int(n), int(n_rel)
+        if not (head.shape == tail.shape == rel.shape):
+            raise ValueError('RelGraph: head, tail and rel must have one length, got %d / %d / %d' % (head.size, tail.size, rel.size))
+        if n < 1 or n_rel < 1 or n >= 2 ** 31 - 1 or head.size >= 2 ** 31 - 1:
+            raise ValueError('RelGraph: N = %d, R = %d, E = %d outside int32 indexing (N, R >= 1)' % (n, n_rel, head.size))
+        if head.size and (head.min() < 0 or head.max() >= n or tail.min() < 0 or tail.max() >= n):
+            raise ValueError('RelGraph: an entity id lies outside [0, %d)' % n)
+        if rel.size and (rel.min() < 0 or rel.max() >= n_rel):
+            raise ValueError('RelGraph: a relation id lies outside [0, %d)' % n_rel)
+        self.n, self.n_rel, self.n_edges = n, n_rel, int(head.size)
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.head, self.tail, self.rel =(torch.from_numpy(a).to(self.device) for a in (head, tail, rel))
+        self.by_head = self.by_tail = self.by_rel = None
+        if self.device.type == 'cuda':
+            self.by_head = RelEdgeList(head, tail, rel, n, self.device)
+            self.by_tail = RelEdgeList(tail, head, rel, n, self.device)
+            self.by_rel = RelEdgeList(rel, head, tail, n_rel, self.device)
+
+    def host_lists(self):
+        """(by_head, by_tail, by_rel) built on the CPU whatever the graph's device: for tests of the orders without a GPU"""
+        h, t, r = self.head.cpu().numpy(), self.tail.cpu().numpy(), self.rel.cpu().numpy()
+        return RelEdgeList(h, t, r, self.n, 'cpu'), RelEdgeList(t, h, r, self.n, 'cpu'), RelEdgeList(r, h, t, self.n_rel, 'cpu')
+
+
 def pattern_of(adj):
     """EdgePattern of a torch sparse adjacency, built once and cached ON the tensor object (like graph_of)"""
     if isinstance(adj, EdgePattern):

@@ -2948,6 +2948,205 @@ def hier_ssl_loss(em, edge, perms):
 
 
 # ----------------------------------------------------------------------------------------------
+# KGIN (reference models/kg/kgin.py): the relational aggregation over a typed knowledge graph and the factor modulation of the user
+# side (csrc/kgin.hip).  The composed torch expressions below take any dtype and device, run where no kernel exists (embedding sizes
+# outside KGIN_DIMS, CPU tensors, float64) and are what the kernels are measured against (SSLREC_KGIN_FUSED=0).
+# ----------------------------------------------------------------------------------------------
+KGIN_DIMS = (32, 64, 128)
+KGIN_FMAX = 8
+KGIN_FUSED = os.environ.get('SSLREC_KGIN_FUSED', '1') != '0'      # 0: the composed torch expressions at every size (measurement)
+
+
+def kgin_fused_ok(d):
+    """embedding sizes csrc/kgin.hip has kernels for"""
+    return int(d) in KGIN_DIMS
+
+
+def _kgin_kernel_path(*tensors):
+    x = tensors[0]
+    return (KGIN_FUSED and x.is_cuda and x.dim() == 2 and kgin_fused_ok(x.shape[1]) and 1 <= x.shape[0] < 2 ** 31 - 1
+            and all(t.is_cuda and t.dtype == torch.float32 for t in tensors))
+
+
+def _kept_edges(graph, keep):
+    h, t, r = graph.head, graph.tail, graph.rel
+    if keep is not None:
+        sel = keep.to(h.device).bool()
+        h, t, r = h[sel], t[sel], r[sel]
+    return h, t, r
+
+
+def _rel_aggregate_composed(graph, x, w, keep=None):
+    """scatter_mean as index_add_ divided by the clamped count (there is no torch_scatter): the [E, d] gather and product exist here.
+    On a HIP device index_add_ and the backward of the two gathers add with float atomics in an order that changes from call to call;
+    there the same expression and its gradient run with torch's deterministic algorithms switched on for the duration of the call
+    (_RelAggregateComposedFn), so this form too gives the same bits twice."""
+    if x.is_cuda:
+        return _RelAggregateComposedFn.apply(x, w, graph, keep)
+    h, t, r = _kept_edges(graph, keep)
+    msg = x[t] * w[r]
+    y = torch.zeros(graph.n, x.shape[1], dtype=x.dtype, device=x.device).index_add_(0, h, msg)
+    cnt = torch.zeros(graph.n, dtype=x.dtype, device=x.device).index_add_(0, h, torch.ones(h.numel(), dtype=x.dtype, device=x.device))
+    return y / cnt.clamp(min=1).unsqueeze(1)
+
+
+class _DeterministicTorch:
+    """torch.use_deterministic_algorithms(True) for a block, the previous setting restored afterwards"""
+
+    def __enter__(self):
+        self.was = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+        torch.use_deterministic_algorithms(True)
+
+    def __exit__(self, *exc):
+        torch.use_deterministic_algorithms(self.was[0], warn_only=self.was[1])
+
+
+class _RelAggregateComposedFn(torch.autograd.Function):
+    """the composed expression and its gradient on a HIP device, every index_add_ in torch's deterministic form"""
+
+    @staticmethod
+    def forward(ctx, x, w, graph, keep):
+        h, t, r = _kept_edges(graph, keep)
+        with _DeterministicTorch():
+            y = torch.zeros(graph.n, x.shape[1], dtype=x.dtype, device=x.device).index_add_(0, h, x[t] * w[r])
+            cnt = torch.zeros(graph.n, dtype=x.dtype, device=x.device).index_add_(0, h, torch.ones(h.numel(), dtype=x.dtype, device=x.device))
+        inv = 1 / cnt.clamp(min=1).unsqueeze(1)
+        ctx.graph, ctx.keep = graph, keep
+        ctx.save_for_backward(x, w, inv)
+        return y * inv
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, inv = ctx.saved_tensors
+        h, t, r = _kept_edges(ctx.graph, ctx.keep)
+        ge = (g * inv)[h]
+        dx = dw = None
+        with _DeterministicTorch():
+            if ctx.needs_input_grad[0]:
+                dx = torch.zeros_like(x).index_add_(0, t, ge * w[r])
+            if ctx.needs_input_grad[1]:
+                dw = torch.zeros_like(w).index_add_(0, r, ge * x[t])
+        return dx, dw, None, None
+
+
+class _RelAggregateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, graph, keep):
+        x, w = _mhcn_table(x), _mhcn_table(w)
+        N, d = x.shape
+        dev = x.device
+        ls = graph.by_head
+        y = torch.empty(N, d, dtype=torch.float32, device=dev)
+        cnt = torch.empty(N, dtype=torch.int32, device=dev)
+        part = torch.empty(max(ls.n_chunks, 1), d, dtype=torch.float32, device=dev)
+        part_cnt = torch.empty(max(ls.n_chunks, 1), dtype=torch.int32, device=dev)
+        rc = _lib.load().sslrec_kgin_rel_fwd_f32(*ls.c_args(), x.data_ptr(), w.data_ptr(), w.shape[0], d, _ptr(keep) or None, cnt.data_ptr(),
+                                                 y.data_ptr(), part.data_ptr(), part_cnt.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_kgin_rel_fwd_f32')
+        ctx.graph, ctx.keep = graph, keep
+        ctx.save_for_backward(x, w, cnt)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, cnt = ctx.saved_tensors
+        graph, keep = ctx.graph, ctx.keep
+        g = _mhcn_table(g)
+        N, d = x.shape
+        dev = x.device
+        lib = _lib.load()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            ls = graph.by_tail
+            dx = torch.empty(N, d, dtype=torch.float32, device=dev)
+            part = torch.empty(max(ls.n_chunks, 1), d, dtype=torch.float32, device=dev)
+            rc = lib.sslrec_kgin_rel_bwd_f32(*ls.c_args(), g.data_ptr(), w.data_ptr(), w.shape[0], 1, d, _ptr(keep) or None, cnt.data_ptr(),
+                                             dx.data_ptr(), part.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_kgin_rel_bwd_f32 (dX)')
+        if ctx.needs_input_grad[1]:
+            ls = graph.by_rel
+            dw = torch.empty(w.shape[0], d, dtype=torch.float32, device=dev)
+            part = torch.empty(max(ls.n_chunks, 1), d, dtype=torch.float32, device=dev)
+            rc = lib.sslrec_kgin_rel_bwd_f32(*ls.c_args(), g.data_ptr(), x.data_ptr(), N, 0, d, _ptr(keep) or None, cnt.data_ptr(),
+                                             dw.data_ptr(), part.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_kgin_rel_bwd_f32 (dW)')
+        return dx, dw, None, None
+
+
+def rel_aggregate(graph, x, w, keep=None):
+    """Y [N, d] with Y[h] = the mean over the kept edges (h, t, r) of x[t] * w[r], 0 for a head without a kept edge: kgin.py:33-36
+    (`scatter_mean(entity_emb[tail] * weight[edge_type - 1], head)`) on a graph.RelGraph whose `rel` is already edge_type - 1.
+    x [N, d], w [R, d]; keep: None or one flag per edge (bool / uint8 [E]) in the ORDER THE GRAPH WAS BUILT FROM -- the edge sample of
+    `_edge_sampling` as a mask; the kernels read it through the edge ids, so a new sample rebuilds nothing.  Differentiable in x and w.
+
+    One CSR walk each for Y, dX and dW (by head, by tail, by relation): no [E, d] tensor, no float atomics, entries of a row added in the
+    graph's edge order, rows and relation lists of more than 512 entries split into 512-entry chunks whose sums are added in chunk order
+    by a second launch; two calls give the same bits.  The integer count of kept edges per head is written by the forward and reused by
+    the backward.  fp32 HIP tensors with d in {32, 64, 128} run csrc/kgin.hip (kgin_fused_ok); everything else, and SSLREC_KGIN_FUSED=0,
+    the composed torch expression (index_add_ and a clamped count, which does form the [E, d] product)."""
+    if x.dim() != 2 or w.dim() != 2 or x.shape[0] != graph.n or w.shape[0] != graph.n_rel or w.shape[1] != x.shape[1]:
+        raise ValueError('rel_aggregate: x [%d, d] and w [%d, d] expected, got %s and %s' % (graph.n, graph.n_rel, tuple(x.shape), tuple(w.shape)))
+    if keep is not None:
+        if keep.dim() != 1 or keep.numel() != graph.n_edges or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('rel_aggregate: keep must hold one bool / uint8 flag per edge (%d)' % graph.n_edges)
+    if _kgin_kernel_path(x, w) and graph.by_head is not None and graph.device == x.device:
+        if keep is not None:
+            keep = keep.to(x.device).to(torch.uint8).contiguous()
+        return _RelAggregateFn.apply(x, w, graph, keep)
+    return _rel_aggregate_composed(graph, x, w, keep)
+
+
+def _factor_modulate_composed(agg, u, latent, dmat):
+    p = torch.softmax(u @ latent.t(), dim=1)
+    return agg * (p @ dmat) + agg
+
+
+class _FactorModulateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, agg, u, latent, dmat):
+        agg, u, latent, dmat = _mhcn_table(agg), _mhcn_table(u), _mhcn_table(latent), _mhcn_table(dmat)
+        U, d = agg.shape
+        out = torch.empty_like(agg)
+        rc = _lib.load().sslrec_kgin_fm_fwd_f32(agg.data_ptr(), u.data_ptr(), latent.data_ptr(), dmat.data_ptr(), U, d, latent.shape[0],
+                                                out.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_kgin_fm_fwd_f32')
+        ctx.save_for_backward(agg, u, latent, dmat)          # (the inputs only: the backward recomputes the softmax)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        agg, u, latent, dmat = ctx.saved_tensors
+        g = _mhcn_table(g)
+        U, d = agg.shape
+        F_ = latent.shape[0]
+        lib = _lib.load()
+        d_agg, d_u = torch.empty_like(agg), torch.empty_like(u)
+        d_ld = torch.empty(2 * F_, d, dtype=torch.float32, device=agg.device)
+        ws = torch.empty(lib.sslrec_kgin_fm_ws_bytes(U, d, F_) // 4 + 1, dtype=torch.float32, device=agg.device)
+        rc = lib.sslrec_kgin_fm_bwd_f32(agg.data_ptr(), u.data_ptr(), latent.data_ptr(), dmat.data_ptr(), g.data_ptr(), U, d, F_, d_agg.data_ptr(),
+                                        d_u.data_ptr(), d_ld.data_ptr(), ws.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_kgin_fm_bwd_f32')
+        return d_agg, d_u, d_ld[:F_], d_ld[F_:]
+
+
+def factor_modulate(agg, u, latent, dmat):
+    """agg * (softmax(u @ latent.T, dim=1) @ dmat) + agg: kgin.py:38-46 with dmat = softmax(disen_weight_att, -1) @ weight [F, d] formed
+    by the caller once per forward (so autograd carries its gradient to both parameters).  agg, u [U, d]; latent [F, d].
+    Differentiable in all four.
+
+    One launch forward, without the [U, F, d] tensor the reference expands; the backward is one launch over the rows, which recomputes
+    the softmax, plus the fixed-order finish of the two [F, d] sums over rows (per-workgroup slabs, no float atomics): two calls give the
+    same bits.  fp32 HIP tensors with d in {32, 64, 128} and F <= 8 run csrc/kgin.hip; everything else, and SSLREC_KGIN_FUSED=0, the
+    composed torch expression."""
+    if agg.dim() != 2 or u.shape != agg.shape or latent.dim() != 2 or latent.shape[1] != agg.shape[1] or dmat.shape != latent.shape:
+        raise ValueError('factor_modulate: agg, u [U, d] and latent, dmat [F, d] expected, got %s, %s, %s, %s' %
+                         (tuple(agg.shape), tuple(u.shape), tuple(latent.shape), tuple(dmat.shape)))
+    if _kgin_kernel_path(agg, u, latent, dmat) and 1 <= latent.shape[0] <= KGIN_FMAX:
+        return _FactorModulateFn.apply(agg, u, latent, dmat)
+    return _factor_modulate_composed(agg, u, latent, dmat)
+
+
+# ----------------------------------------------------------------------------------------------
 # all-rank evaluation and negative sampling on the device (SURVEY.md §8f ranks 2 and 3)
 # ----------------------------------------------------------------------------------------------
 def full_predict(user_table, item_table, users, train_mask=None):

@@ -1066,6 +1066,46 @@ size_t sslrec_kgin_fm_ws_bytes(int32_t U, int32_t d, int32_t F);
 int sslrec_kgin_fm_bwd_f32(const float *agg, const float *u, const float *latent, const float *Dm, const float *gout, int32_t U, int32_t d, int32_t F,
                            float *d_agg, float *d_u, float *d_latent_and_d, void *ws, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * KGCL's relation-aware graph attention (csrc/rgat.hip), models/kg/kgcl.py.  Tables are [*, d] fp32 row-major, 16-byte aligned, d in
+ * {32, 64, 128}; slope >= 0.  The edge lists are those of the KGIN entries above (one order of a graph.RelGraph each, chunks of
+ * SSLREC_KGIN_CHUNK slots for the long destinations, `keep` read through eid, NULL = every edge).  No float atomics; two calls give the
+ * same bits.  SSLREC_E_BADARG before any launch for a null pointer, a misaligned table or a shape outside these ranges.
+ *
+ * Forward, kgcl.py:60-72 (RGAT.agg):
+ *     a_input = cat([entity_emb[head], entity_emb[tail]], -1);  e_input = (fc(a_input) * relation_emb[edge_type]).sum(-1)
+ *     e = scatter_softmax(leakyrelu(e_input), head);  agg_emb = scatter_sum(entity_emb[tail] * e.view(-1, 1), head)
+ * with fc(cat(x[h], x[t])) = P[h] + Q[t], the node tables P = X Wh^T + b and Q = X Wt^T formed by the caller.  The list ordered by head
+ * (ia = tail, ib = relation).  Written: Y [n_dest, d]; S [E] by EDGE ID, the logit after the LeakyReLU of every kept edge (other entries
+ * are left alone); M, Z [n_dest], the maximum and the sum of exp(S - M) over the head's kept edges (Z = 0, M = 0, Y = 0 for a head
+ * without one).  part [n_chunks, d] and part_mz [n_chunks, 2] take the chunks' (acc, m, z), merged in chunk order by a second launch.
+ * R [n_rel, d] sits in LDS when it fits 48 KiB. */
+int sslrec_rgat_fwd_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                        const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest, const int32_t *long_ptr,
+                        int32_t n_long, const float *X, const float *P, const float *Q, const float *R, int32_t n_rel, int32_t d, float slope,
+                        const uint8_t *keep, float *S, float *M, float *Z, float *Y, float *part, float *part_mz, void *stream);
+
+/* The backward of the same lines (what autograd derives from scatter_softmax / scatter_sum / the two gathers), three walks from G = dY.
+ * By head (the forward's list): alpha [E] and dl [E] by edge id for the kept edges, alpha_e = exp(S_e - M_h) / Z_h,
+ * dl_e = alpha_e (<G[h], X[t]> - <G[h], Y[h]>) (S_e > 0 ? 1 : slope), and dP[h] = sum dl_e R[r].  part [n_chunks, d]. */
+int sslrec_rgat_bwd_head_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                             const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                             const int32_t *long_ptr, int32_t n_long, const float *X, const float *R, int32_t n_rel, int32_t d, float slope,
+                             const uint8_t *keep, const float *G, const float *Y, const float *S, const float *M, const float *Z, float *alpha,
+                             float *dl, float *dP, float *part, void *stream);
+
+/* By tail (ia = head, ib = relation): dX[t] = sum alpha_e G[h] and dQ[t] = sum dl_e R[r] in one walk.  part [n_chunks, 2, d]. */
+int sslrec_rgat_bwd_tail_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                             const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                             const int32_t *long_ptr, int32_t n_long, const float *G, const float *R, int32_t n_rel, int32_t d, const uint8_t *keep,
+                             const float *alpha, const float *dl, float *dX, float *dQ, float *part, void *stream);
+
+/* By relation (ia = head, ib = tail): dR[r] = sum dl_e (P[h] + Q[t]).  part [n_chunks, d]. */
+int sslrec_rgat_bwd_rel_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                            const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                            const int32_t *long_ptr, int32_t n_long, const float *P, const float *Q, int32_t d, const uint8_t *keep, const float *dl,
+                            float *dR, float *part, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,11 @@ SIGNATURES = {
     'sslrec_kgin_fm_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     'sslrec_kgin_fm_ws_bytes': (C.c_size_t, [_I, _I, _I]),
     'sslrec_kgin_fm_bwd_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'sslrec_rgat_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rgat_bwd_head_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P]),
+    'sslrec_rgat_bwd_tail_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rgat_bwd_rel_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

@@ -3147,6 +3147,152 @@ def factor_modulate(agg, u, latent, dmat):
 
 
 # ----------------------------------------------------------------------------------------------
+# KGCL (reference models/kg/kgcl.py): the relation-aware graph attention RGAT.agg (:60-72) over a RelGraph (csrc/rgat.hip).  The
+# composed torch expression takes any dtype and device, runs where no kernel exists (embedding sizes outside KGIN_DIMS, CPU tensors,
+# float64) and is what the kernels are measured against (SSLREC_KGCL_FUSED=0).
+# ----------------------------------------------------------------------------------------------
+KGCL_FUSED = os.environ.get('SSLREC_KGCL_FUSED', '1') != '0'      # 0: the composed torch expression at every size (measurement)
+
+
+def _rel_attention_expr(graph, x, p, q, r, keep, slope):
+    """the contract of rel_attention in torch: scatter_softmax as exp(s - max of the head) over an index_add_ of the same, scatter_sum as
+    index_add_ (there is no torch_scatter); the [E, d] gathers and products exist here.  The per-head maximum is a constant of the
+    softmax (a shift changes nothing), so it is taken of the detached logits."""
+    h, t, rr = _kept_edges(graph, keep)
+    n = graph.n
+    s = torch.nn.functional.leaky_relu(((p[h] + q[t]) * r[rr]).sum(-1), slope)
+    mx = torch.full((n,), float('-inf'), dtype=s.dtype, device=s.device).scatter_reduce_(0, h, s.detach(), 'amax', include_self=True)
+    e = torch.exp(s - mx[h])
+    z = torch.zeros(n, dtype=s.dtype, device=s.device).index_add_(0, h, e)
+    return torch.zeros(n, x.shape[1], dtype=x.dtype, device=x.device).index_add_(0, h, x[t] * (e / z[h]).unsqueeze(1))
+
+
+class _RelAttentionComposedFn(torch.autograd.Function):
+    """the composed expression and its gradient on a HIP device with torch's deterministic algorithms switched on for the duration of both
+    (as _RelAggregateComposedFn): the inner graph is built in the forward and differentiated in the backward"""
+
+    @staticmethod
+    def forward(ctx, x, p, q, r, graph, keep, slope):
+        inner = [a.detach().requires_grad_(need) for a, need in zip((x, p, q, r), ctx.needs_input_grad[:4])]
+        with _DeterministicTorch(), torch.enable_grad():
+            y = _rel_attention_expr(graph, *inner, keep, slope)
+        ctx.inner, ctx.y = inner, y
+        return y.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        wanted = [a for a in ctx.inner if a.requires_grad]
+        with _DeterministicTorch():
+            grads = iter(torch.autograd.grad(ctx.y, wanted, g, retain_graph=True))
+        return (*[next(grads) if a.requires_grad else None for a in ctx.inner], None, None, None)
+
+
+def _rel_attention_composed(graph, x, p, q, r, keep=None, slope=0.2):
+    if x.is_cuda:
+        return _RelAttentionComposedFn.apply(x, p, q, r, graph, keep, slope)
+    return _rel_attention_expr(graph, x, p, q, r, keep, slope)
+
+
+class _RelAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, q, r, graph, keep, slope):
+        x, p, q, r = _mhcn_table(x), _mhcn_table(p), _mhcn_table(q), _mhcn_table(r)
+        N, d = x.shape
+        dev = x.device
+        ls = graph.by_head
+        y = torch.empty(N, d, dtype=torch.float32, device=dev)
+        s = torch.empty(max(graph.n_edges, 1), dtype=torch.float32, device=dev)
+        m = torch.empty(N, dtype=torch.float32, device=dev)
+        z = torch.empty(N, dtype=torch.float32, device=dev)
+        part = torch.empty(max(ls.n_chunks, 1), d, dtype=torch.float32, device=dev)
+        part_mz = torch.empty(max(ls.n_chunks, 1), 2, dtype=torch.float32, device=dev)
+        rc = _lib.load().sslrec_rgat_fwd_f32(*ls.c_args(), x.data_ptr(), p.data_ptr(), q.data_ptr(), r.data_ptr(), r.shape[0], d, slope,
+                                             _ptr(keep) or None, s.data_ptr(), m.data_ptr(), z.data_ptr(), y.data_ptr(), part.data_ptr(),
+                                             part_mz.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_rgat_fwd_f32')
+        ctx.graph, ctx.keep, ctx.slope = graph, keep, slope
+        ctx.save_for_backward(x, p, q, r, y, s, m, z)          # tables, Y and [E]- / [N]-sized vectors: no [E, d] tensor
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, p, q, r, y, s, m, z = ctx.saved_tensors
+        graph, keep, slope = ctx.graph, ctx.keep, ctx.slope
+        g = _mhcn_table(g)
+        N, d = x.shape
+        dev = x.device
+        lib = _lib.load()
+        kp = _ptr(keep) or None
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        alpha, dl = new(max(graph.n_edges, 1)), new(max(graph.n_edges, 1))
+        ls = graph.by_head
+        dp, part = new(N, d), new(max(ls.n_chunks, 1), d)
+        rc = lib.sslrec_rgat_bwd_head_f32(*ls.c_args(), x.data_ptr(), r.data_ptr(), r.shape[0], d, slope, kp, g.data_ptr(), y.data_ptr(),
+                                          s.data_ptr(), m.data_ptr(), z.data_ptr(), alpha.data_ptr(), dl.data_ptr(), dp.data_ptr(),
+                                          part.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_rgat_bwd_head_f32')
+        dx = dq = dr = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            ls = graph.by_tail
+            dx, dq, part = new(N, d), new(N, d), new(max(ls.n_chunks, 1), 2, d)
+            rc = lib.sslrec_rgat_bwd_tail_f32(*ls.c_args(), g.data_ptr(), r.data_ptr(), r.shape[0], d, kp, alpha.data_ptr(), dl.data_ptr(),
+                                              dx.data_ptr(), dq.data_ptr(), part.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_rgat_bwd_tail_f32')
+        if ctx.needs_input_grad[3]:
+            ls = graph.by_rel
+            dr, part = new(r.shape[0], d), new(max(ls.n_chunks, 1), d)
+            rc = lib.sslrec_rgat_bwd_rel_f32(*ls.c_args(), p.data_ptr(), q.data_ptr(), d, kp, dl.data_ptr(), dr.data_ptr(), part.data_ptr(),
+                                             _stream())
+            _lib.check(rc, 'sslrec_rgat_bwd_rel_f32')
+        return dx, dp, dq, dr, None, None, None
+
+
+def rel_attention(graph, x, p, q, r, keep=None, slope=0.2):
+    """Y [N, d], the edge softmax attention of kgcl.py:60-72 (RGAT.agg) over a graph.RelGraph, with the node tables p = x Wh^T + b and
+    q = x Wt^T in place of the per-edge fc(cat(x[head], x[tail])) (ops.rgat_aggregate forms them).  Over the kept edges e = (h, t, rel):
+
+        l_e = <p[h] + q[t], r[rel]>,  s_e = l_e > 0 ? l_e : slope l_e,  a_e = softmax of s over the kept edges of head h,
+        Y[h] = sum a_e x[t]    (0 for a head without a kept edge)
+
+    x, p, q [N, d], r [R, d]; keep as in rel_aggregate: None or one bool / uint8 flag per edge in the order the graph was built from, read
+    through the edge ids, so a new mask rebuilds nothing.  Differentiable in x, p, q and r.
+
+    fp32 HIP tensors with d in {32, 64, 128} and slope >= 0 run csrc/rgat.hip: one CSR walk by head forward (online softmax; a head of
+    more than 512 slots in 512-slot chunks merged in chunk order), and backward one walk each by head (dp, and a_e and dl_e as [E]
+    vectors), by tail (dx and dq) and by relation (dr), long lists chunked the same way.  No [E, d] tensor, no float atomics, two calls
+    give the same bits.  Everything else, and SSLREC_KGCL_FUSED=0 / ops.KGCL_FUSED = False, runs the composed torch expression
+    (index_add_, a per-head amax through scatter_reduce_; on a HIP device under torch's deterministic algorithms)."""
+    d = x.shape[1] if x.dim() == 2 else -1
+    if x.dim() != 2 or x.shape[0] != graph.n or p.shape != x.shape or q.shape != x.shape or r.dim() != 2 or tuple(r.shape) != (graph.n_rel, d):
+        raise ValueError('rel_attention: x, p, q [%d, d] and r [%d, d] expected, got %s, %s, %s and %s' %
+                         (graph.n, graph.n_rel, tuple(x.shape), tuple(p.shape), tuple(q.shape), tuple(r.shape)))
+    if keep is not None:
+        if keep.dim() != 1 or keep.numel() != graph.n_edges or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('rel_attention: keep must hold one bool / uint8 flag per edge (%d)' % graph.n_edges)
+    slope = float(slope)
+    if (KGCL_FUSED and slope >= 0 and x.is_cuda and kgin_fused_ok(d) and all(t.is_cuda and t.dtype == torch.float32 for t in (x, p, q, r))
+            and graph.by_head is not None and graph.device == x.device):
+        if keep is not None:
+            keep = keep.to(x.device).to(torch.uint8).contiguous()
+        return _RelAttentionFn.apply(x, p, q, r, graph, keep, slope)
+    return _rel_attention_composed(graph, x, p, q, r, keep, slope)
+
+
+def rgat_aggregate(graph, x, fc_weight, fc_bias, rel_emb, keep=None, slope=0.2):
+    """RGAT.agg (kgcl.py:60-72) from the module's parameters: fc_weight [d, 2 d] and fc_bias [d] of `fc = Linear(2 d, d)`, rel_emb [R, d]
+    the rows the graph's relation ids index.  fc(cat(x[h], x[t])) = x[h] Wh^T + b + x[t] Wt^T with Wh = fc_weight[:, :d] and
+    Wt = fc_weight[:, d:], so P = x Wh^T + b and Q = x Wt^T are two [N, d] matmuls and autograd carries dP and dQ to x, fc_weight and
+    fc_bias; the rest is rel_attention."""
+    d = x.shape[1]
+    if tuple(fc_weight.shape) != (d, 2 * d) or tuple(fc_bias.shape) != (d,):
+        raise ValueError('rgat_aggregate: fc_weight [%d, %d] and fc_bias [%d] expected, got %s and %s' %
+                         (d, 2 * d, d, tuple(fc_weight.shape), tuple(fc_bias.shape)))
+    p = torch.addmm(fc_bias, x, fc_weight[:, :d].t())
+    q = x @ fc_weight[:, d:].t()
+    return rel_attention(graph, x, p, q, rel_emb, keep, slope)
+
+
+# ----------------------------------------------------------------------------------------------
 # all-rank evaluation and negative sampling on the device (SURVEY.md §8f ranks 2 and 3)
 # ----------------------------------------------------------------------------------------------
 def full_predict(user_table, item_table, users, train_mask=None):

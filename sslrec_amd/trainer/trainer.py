@@ -197,6 +197,10 @@ class Trainer(object):
             from ..rng import flush_host_replay
             flush_host_replay()
 
+    def _epoch_extras(self, model):
+        """what a trainer appends to every batch of the epoch that starts (KGCLTrainer: the epoch's augmented views); nothing here"""
+        return []
+
     def _train_epoch_eager(self, model, epoch_idx):
         """reference trainer/trainer.py:51-84.  The reference reads `loss.item()` (and every logged part) in every step: three device
         synchronisations per step, during which the host cannot queue the next step's launches.  Here the step's 0-d tensors are kept and
@@ -206,10 +210,11 @@ class Trainer(object):
         loader.dataset.sample_negs()
         n_batches = len(loader)
         model.train()
+        extras = self._epoch_extras(model)
         kept, names = [], None
         for tem in loader:
             self.optimizer.zero_grad()
-            batch_data = [x.long().to(configs['device']) for x in tem]
+            batch_data = [x.long().to(configs['device']) for x in tem] + extras
             loss, loss_dict = model.cal_loss(batch_data)
             self._backward(loss)
             self.optimizer.step()
@@ -452,6 +457,15 @@ class GFormerTrainer(Trainer):
         steps = max(1, len(loader.dataset) // configs['train']['batch_size'])
         writer.add_scalar('Loss/train', ep_loss / steps, epoch_idx)
         self.logger.log_loss(epoch_idx, loss_log, save_to_log=bool(configs['train']['log_loss']))
+
+
+class KGCLTrainer(Trainer):
+    """reference trainer/trainer.py:495-575 without its `train_trans` half: `Trainer.train_epoch` with `model.get_aug_views()` called once
+    per epoch, after the negatives are sampled and before the batch loop, and the four views appended to every batch (:517-521).  One
+    optimizer: upstream's second one, `kgtrans_optimizer`, only steps under `train_trans`, which the kg data handler refuses."""
+
+    def _epoch_extras(self, model):
+        return list(model.get_aug_views())
 
 
 class AdaGCLTrainer(Trainer):

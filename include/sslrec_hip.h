@@ -1106,6 +1106,65 @@ int sslrec_rgat_bwd_rel_f32(const int32_t *ptr, const int32_t *ia, const int32_t
                             const int32_t *long_ptr, int32_t n_long, const float *P, const float *Q, int32_t d, const uint8_t *keep, const float *dl,
                             float *dR, float *part, void *stream);
 
+/* ----------------------------------------------------------------------------------------------------------------------------------
+ * KGRec's two-head relational attention (csrc/rmha.hip), models/kg/kgrec.py.  Tables are [*, d] fp32 row-major, 16-byte aligned, d in
+ * {32, 64, 128}, exactly two attention heads: head a owns the columns [a d/2, (a + 1) d/2), c = 1 / sqrt(d / 2).  The edge lists are
+ * those of the KGIN entries above (one order of a graph.RelGraph each, chunks of SSLREC_KGIN_CHUNK slots for the long destinations,
+ * `keep` read through eid, NULL = every edge).  No float atomics; two calls give the same bits.  SSLREC_E_BADARG before any launch for
+ * a null pointer, a misaligned table or a shape outside these ranges.
+ *
+ * Forward, kgrec.py:63-82 (AttnHGCN.shared_layer_agg):
+ *     query = (entity_emb[head] @ W_Q).view(-1, 2, d_k);  key = (entity_emb[tail] @ W_Q).view(-1, 2, d_k) * relation_emb[edge_type - 1]
+ *     edge_attn_score = scatter_softmax((query * key).sum(-1) / sqrt(d_k), head)
+ *     entity_agg = scatter_sum((entity_emb[tail] * relation_emb[edge_type - 1]).view(-1, 2, d_k) * edge_attn_score, head)
+ * with the node table T = X W_Q formed by the caller.  The list ordered by head (ia = tail, ib = relation).  Written: Y [n_dest, d];
+ * Lg [E, 2] by EDGE ID, the two logits of every kept edge (other entries are left alone); M, Z [n_dest, 2], the maximum and the sum of
+ * exp(Lg - M) over the head entity's kept edges per attention head (Z = 0, M = 0, Y = 0 without one).  part [n_chunks, d] and part_mz
+ * [n_chunks, 2, 2] take the chunks' acc and (m, z) per attention head, merged in chunk order by a second launch.  R [n_rel, d] sits in
+ * LDS when it fits 48 KiB. */
+int sslrec_rmha_fwd_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                        const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest, const int32_t *long_ptr,
+                        int32_t n_long, const float *X, const float *T, const float *R, int32_t n_rel, int32_t d, const uint8_t *keep, float *Lg,
+                        float *M, float *Z, float *Y, float *part, float *part_mz, void *stream);
+
+/* The backward of the same lines (what autograd derives from the softmax, the scatter_sum and the gathers), three walks from G = dY.
+ * By head (the forward's list): alpha [E, 2] and dl [E, 2] by edge id for the kept edges, alpha_ea = exp(Lg_ea - M_ha) / Z_ha,
+ * dl_ea = alpha_ea (sum_{C_a} G[h] X[t] R[r] - sum_{C_a} G[h] Y[h]), and dT[h] = c sum dl_ea T[t] R[r].  part [n_chunks, d]. */
+int sslrec_rmha_bwd_head_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                             const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                             const int32_t *long_ptr, int32_t n_long, const float *X, const float *T, const float *R, int32_t n_rel, int32_t d,
+                             const uint8_t *keep, const float *G, const float *Y, const float *Lg, const float *M, const float *Z, float *alpha,
+                             float *dl, float *dT, float *part, void *stream);
+
+/* By tail (ia = head, ib = relation): dX[t] = sum alpha_ea G[h] R[r] and dT[t] = c sum dl_ea T[h] R[r] in one walk (the caller adds the
+ * two halves of dT).  part [n_chunks, 2, d]. */
+int sslrec_rmha_bwd_tail_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                             const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                             const int32_t *long_ptr, int32_t n_long, const float *G, const float *T, const float *R, int32_t n_rel, int32_t d,
+                             const uint8_t *keep, const float *alpha, const float *dl, float *dX, float *dT, float *part, void *stream);
+
+/* By relation (ia = head, ib = tail): dR[r] = sum (c dl_ea T[h] T[t] + alpha_ea G[h] X[t]).  part [n_chunks, d]. */
+int sslrec_rmha_bwd_rel_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                            const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                            const int32_t *long_ptr, int32_t n_long, const float *G, const float *X, const float *T, int32_t d, const uint8_t *keep,
+                            const float *alpha, const float *dl, float *dR, float *part, void *stream);
+
+/* The rationale scores, kgrec.py:165-188 (norm_attn_computer, under no_grad), on the list ordered by head:
+ *     edge_attn_logits = ((query * key).sum(-1) / sqrt(d_k)).mean(-1);  edge_attn_score = scatter_softmax(edge_attn_logits, head) * degree[head]
+ * logit, score [E] by edge id for the kept edges (the caller zeroes both first); mean_head [n_dest], the mean of the scores over the head
+ * entity's kept edges, 0 without one (the scatter_mean of kgrec.py:414), evaluated as Z (count / Z) / count: the scores of one entity add
+ * up to (count / Z) sum exp(l - M).  part_mz [n_chunks, 2], part_cnt [n_chunks]. */
+int sslrec_rmha_score_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                          const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest,
+                          const int32_t *long_ptr, int32_t n_long, const float *T, const float *R, int32_t n_rel, int32_t d, const uint8_t *keep,
+                          float *logit, float *score, float *mean_head, float *part_mz, int32_t *part_cnt, void *stream);
+
+/* mean [n_dest]: the mean of score (by edge id) over the kept slots of every destination of a list, 0 without one; on the list ordered
+ * by tail the scatter_mean of kgrec.py:416.  part_sum, part_cnt [n_chunks]. */
+int sslrec_rmha_mean_f32(const int32_t *ptr, const int32_t *ia, const int32_t *ib, const int32_t *eid, int32_t n_dest, int64_t n_slots,
+                         const int32_t *chunk_dest, const int32_t *chunk_begin, int32_t n_chunks, const int32_t *long_dest, const int32_t *long_ptr,
+                         int32_t n_long, const uint8_t *keep, const float *score, float *mean, float *part_sum, int32_t *part_cnt, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
     python main.py --model mhcn [--dataset ciao|epinions|yelp|lastfm] [--synthetic social-yelp|social-epinions|social-tiny]
     python main.py --model kgin [--dataset mind|alibaba-fashion|last-fm] [--synthetic kg-last-fm|kg-alibaba|kg-tiny]
     python main.py --model kgcl [--dataset mind|alibaba-fashion|last-fm] [--synthetic kg-last-fm|kg-alibaba|kg-tiny]
+    python main.py --model kgrec [--dataset mind|alibaba-fashion|last-fm] [--synthetic kg-last-fm|kg-alibaba|kg-tiny]
 
 Datasets are read from `./datasets/general_cf/sparse_*/{train,valid,test}_mat.pkl` (social models:
 `./datasets/social/*/{trn,tst,trust}_mat.pkl`; kg models: `./datasets/kg/*_kg/{train,test,kg_final}.txt`)

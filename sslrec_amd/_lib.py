@@ -228,6 +228,13 @@ SIGNATURES = {
                                            _P, _P, _P, _P]),
     'sslrec_rgat_bwd_tail_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'sslrec_rgat_bwd_rel_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'sslrec_rmha_fwd_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rmha_bwd_head_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P]),
+    'sslrec_rmha_bwd_tail_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rmha_bwd_rel_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rmha_score_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'sslrec_rmha_mean_f32': (C.c_int, [_P, _P, _P, _P, _I, C.c_int64, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 EDGE_MLP_SLOTS = 1024     # SSLREC_EDGE_MLP_SLOTS

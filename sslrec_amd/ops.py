@@ -3293,6 +3293,236 @@ def rgat_aggregate(graph, x, fc_weight, fc_bias, rel_emb, keep=None, slope=0.2):
 
 
 # ----------------------------------------------------------------------------------------------
+# KGRec (reference models/kg/kgrec.py): the two-head relational attention AttnHGCN.shared_layer_agg (:63-88) and the rationale scores
+# norm_attn_computer (:165-188) over a RelGraph (csrc/rmha.hip).  The composed torch expressions take any dtype and device, run where
+# no kernel exists (embedding sizes outside KGIN_DIMS, CPU tensors, float64) and are what the kernels are measured against
+# (SSLREC_KGREC_FUSED=0).
+# ----------------------------------------------------------------------------------------------
+KGREC_FUSED = os.environ.get('SSLREC_KGREC_FUSED', '1') != '0'      # 0: the composed torch expressions at every size (measurement)
+KGREC_HEADS = 2
+
+
+def _mh_logits(graph, t, r, keep):
+    """(h, tail, rel, l [E', 2]) of the kept edges: l_ea = sum over head a's columns of t[h] t[tail] r[rel], over sqrt(d / 2)"""
+    h, tl, rr = _kept_edges(graph, keep)
+    dk = t.shape[1] // KGREC_HEADS
+    key = (t[tl] * r[rr]).view(-1, KGREC_HEADS, dk)
+    return h, tl, rr, (t[h].view(-1, KGREC_HEADS, dk) * key).sum(-1) / math.sqrt(dk)
+
+
+def _head_softmax(h, l, n):
+    """softmax of the rows of l over the edges of each head entity (scatter_softmax); the per-entity maximum is a constant of the softmax
+    and is taken of the detached logits"""
+    idx = h if l.dim() == 1 else h.unsqueeze(1).expand(-1, l.shape[1])
+    mx = torch.full((n,) + tuple(l.shape[1:]), float('-inf'), dtype=l.dtype, device=l.device).scatter_reduce_(0, idx, l.detach(), 'amax',
+                                                                                                             include_self=True)
+    e = torch.exp(l - mx[h])
+    z = torch.zeros((n,) + tuple(l.shape[1:]), dtype=l.dtype, device=l.device).index_add_(0, h, e)
+    return e / z[h]
+
+
+def _rel_mh_attention_expr(graph, x, t, r, keep):
+    """the contract of rel_mh_attention in torch: the [E, d] gathers and products exist here"""
+    h, tl, rr, l = _mh_logits(graph, t, r, keep)
+    n, d = graph.n, x.shape[1]
+    a = _head_softmax(h, l, n)
+    val = (x[tl] * r[rr]).view(-1, KGREC_HEADS, d // KGREC_HEADS) * a.unsqueeze(-1)
+    return torch.zeros(n, d, dtype=x.dtype, device=x.device).index_add_(0, h, val.reshape(-1, d))
+
+
+class _RelMhAttentionComposedFn(torch.autograd.Function):
+    """the composed expression and its gradient on a HIP device with torch's deterministic algorithms switched on for the duration of both
+    (as _RelAttentionComposedFn)"""
+
+    @staticmethod
+    def forward(ctx, x, t, r, graph, keep):
+        inner = [a.detach().requires_grad_(need) for a, need in zip((x, t, r), ctx.needs_input_grad[:3])]
+        with _DeterministicTorch(), torch.enable_grad():
+            y = _rel_mh_attention_expr(graph, *inner, keep)
+        ctx.inner, ctx.y = inner, y
+        return y.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        wanted = [a for a in ctx.inner if a.requires_grad]
+        with _DeterministicTorch():
+            grads = iter(torch.autograd.grad(ctx.y, wanted, g, retain_graph=True))
+        return (*[next(grads) if a.requires_grad else None for a in ctx.inner], None, None)
+
+
+def _rel_mh_attention_composed(graph, x, t, r, keep=None):
+    if x.is_cuda:
+        return _RelMhAttentionComposedFn.apply(x, t, r, graph, keep)
+    return _rel_mh_attention_expr(graph, x, t, r, keep)
+
+
+class _RelMhAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, r, graph, keep):
+        x, t, r = _mhcn_table(x), _mhcn_table(t), _mhcn_table(r)
+        N, d = x.shape
+        dev = x.device
+        ls = graph.by_head
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        y, lg, m, z = new(N, d), new(max(graph.n_edges, 1), 2), new(N, 2), new(N, 2)
+        part, part_mz = new(max(ls.n_chunks, 1), d), new(max(ls.n_chunks, 1), 2, 2)
+        rc = _lib.load().sslrec_rmha_fwd_f32(*ls.c_args(), x.data_ptr(), t.data_ptr(), r.data_ptr(), r.shape[0], d, _ptr(keep) or None,
+                                             lg.data_ptr(), m.data_ptr(), z.data_ptr(), y.data_ptr(), part.data_ptr(), part_mz.data_ptr(),
+                                             _stream())
+        _lib.check(rc, 'sslrec_rmha_fwd_f32')
+        ctx.graph, ctx.keep = graph, keep
+        ctx.save_for_backward(x, t, r, y, lg, m, z)            # tables, Y and [E, 2]- / [N, 2]-sized vectors: no [E, d] tensor
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, r, y, lg, m, z = ctx.saved_tensors
+        graph, keep = ctx.graph, ctx.keep
+        g = _mhcn_table(g)
+        N, d = x.shape
+        dev = x.device
+        lib = _lib.load()
+        kp = _ptr(keep) or None
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        alpha, dl = new(max(graph.n_edges, 1), 2), new(max(graph.n_edges, 1), 2)
+        ls = graph.by_head
+        dt_head, part = new(N, d), new(max(ls.n_chunks, 1), d)
+        rc = lib.sslrec_rmha_bwd_head_f32(*ls.c_args(), x.data_ptr(), t.data_ptr(), r.data_ptr(), r.shape[0], d, kp, g.data_ptr(), y.data_ptr(),
+                                          lg.data_ptr(), m.data_ptr(), z.data_ptr(), alpha.data_ptr(), dl.data_ptr(), dt_head.data_ptr(),
+                                          part.data_ptr(), _stream())
+        _lib.check(rc, 'sslrec_rmha_bwd_head_f32')
+        dx = dt = dr = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ls = graph.by_tail
+            dx, dt_tail, part = new(N, d), new(N, d), new(max(ls.n_chunks, 1), 2, d)
+            rc = lib.sslrec_rmha_bwd_tail_f32(*ls.c_args(), g.data_ptr(), t.data_ptr(), r.data_ptr(), r.shape[0], d, kp, alpha.data_ptr(),
+                                              dl.data_ptr(), dx.data_ptr(), dt_tail.data_ptr(), part.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_rmha_bwd_tail_f32')
+            dt = dt_head.add_(dt_tail)                          # [N, d]: the head's and the tail's share of dT
+        if ctx.needs_input_grad[2]:
+            ls = graph.by_rel
+            dr, part = new(r.shape[0], d), new(max(ls.n_chunks, 1), d)
+            rc = lib.sslrec_rmha_bwd_rel_f32(*ls.c_args(), g.data_ptr(), x.data_ptr(), t.data_ptr(), d, kp, alpha.data_ptr(), dl.data_ptr(),
+                                             dr.data_ptr(), part.data_ptr(), _stream())
+            _lib.check(rc, 'sslrec_rmha_bwd_rel_f32')
+        return (dx if ctx.needs_input_grad[0] else None, dt if ctx.needs_input_grad[1] else None, dr, None, None)
+
+
+def _kgrec_args(name, graph, t, r, keep):
+    d = t.shape[1] if t.dim() == 2 else -1
+    if t.dim() != 2 or t.shape[0] != graph.n or r.dim() != 2 or tuple(r.shape) != (graph.n_rel, d) or d % KGREC_HEADS:
+        raise ValueError('%s: tables [%d, d] with an even d and r [%d, d] expected, got %s and %s' %
+                         (name, graph.n, graph.n_rel, tuple(t.shape), tuple(r.shape)))
+    if keep is not None:
+        if keep.dim() != 1 or keep.numel() != graph.n_edges or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError('%s: keep must hold one bool / uint8 flag per edge (%d)' % (name, graph.n_edges))
+
+
+def _kgrec_kernel_path(graph, *tensors):
+    x = tensors[0]
+    return (KGREC_FUSED and x.is_cuda and kgin_fused_ok(x.shape[1]) and all(a.is_cuda and a.dtype == torch.float32 for a in tensors)
+            and graph.by_head is not None and graph.device == x.device)
+
+
+def rel_mh_attention(graph, x, t, r, keep=None):
+    """Y [N, d], the two-head attention of kgrec.py:63-82 (AttnHGCN.shared_layer_agg, its entity side) over a graph.RelGraph, with the
+    node table t = x W_Q in place of the per-edge `entity_emb[.] @ W_Q` (ops.attn_hgcn_aggregate forms it).  Attention head a owns the
+    columns C_a = [a d/2, (a + 1) d/2).  Over the kept edges e = (h, tail, rel):
+
+        l_ea = sum_{C_a} t[h] t[tail] r[rel] / sqrt(d / 2),   al_ea = softmax of l_.a over the kept edges of head entity h,
+        Y[h]_j = sum_e al_ea(j) x[tail]_j r[rel]_j    (0 for an entity without a kept edge)
+
+    x, t [N, d], r [R, d]; keep as in rel_aggregate: None or one bool / uint8 flag per edge in the order the graph was built from, read
+    through the edge ids, so a new mask rebuilds nothing.  Differentiable in x, t and r.
+
+    fp32 HIP tensors with d in {32, 64, 128} run csrc/rmha.hip: one CSR walk by head forward (online softmax per attention head on the
+    two halves of the lane group; an entity of more than 512 slots in 512-slot chunks merged in chunk order), and backward one walk each
+    by head (dt's head share, and al and dl as [E, 2] vectors), by tail (dx and dt's tail share) and by relation (dr), long lists chunked
+    the same way.  No [E, d] tensor, no float atomics, two calls give the same bits.  Everything else, and SSLREC_KGREC_FUSED=0 /
+    ops.KGREC_FUSED = False, runs the composed torch expression (on a HIP device under torch's deterministic algorithms)."""
+    if tuple(x.shape) != tuple(t.shape):
+        raise ValueError('rel_mh_attention: x and t of one shape expected, got %s and %s' % (tuple(x.shape), tuple(t.shape)))
+    _kgrec_args('rel_mh_attention', graph, t, r, keep)
+    if _kgrec_kernel_path(graph, x, t, r):
+        if keep is not None:
+            keep = keep.to(x.device).to(torch.uint8).contiguous()
+        return _RelMhAttentionFn.apply(x, t, r, graph, keep)
+    return _rel_mh_attention_composed(graph, x, t, r, keep)
+
+
+def attn_hgcn_aggregate(graph, x, w_q, rel_emb, keep=None):
+    """the entity side of AttnHGCN.shared_layer_agg (kgrec.py:63-82) from the module's parameters: w_q [d, d], rel_emb [R, d] the rows the
+    graph's relation ids index.  query and key are rows of T = x @ w_q, one [N, d] matmul through which autograd carries dT to x and
+    w_q; the rest is rel_mh_attention."""
+    d = x.shape[1]
+    if tuple(w_q.shape) != (d, d):
+        raise ValueError('attn_hgcn_aggregate: w_q [%d, %d] expected, got %s' % (d, d, tuple(w_q.shape)))
+    return rel_mh_attention(graph, x, torch.mm(x, w_q), rel_emb, keep)
+
+
+def _rel_rationale_composed(graph, t, r, keep):
+    h, tl, rr, l = _mh_logits(graph, t, r, keep)
+    n, E = graph.n, graph.n_edges
+    lbar = l.mean(-1)
+    ones = torch.ones_like(lbar)
+    deg_h = torch.zeros(n, dtype=t.dtype, device=t.device).index_add_(0, h, ones)
+    deg_t = torch.zeros(n, dtype=t.dtype, device=t.device).index_add_(0, tl, ones)
+    sc = _head_softmax(h, lbar, n) * deg_h[h]
+    if keep is None:
+        score, logits = sc, lbar
+    else:
+        sel = keep.to(t.device).bool()
+        score = torch.zeros(E, dtype=t.dtype, device=t.device).masked_scatter_(sel, sc)
+        logits = torch.zeros(E, dtype=t.dtype, device=t.device).masked_scatter_(sel, lbar)
+    mean_head = torch.zeros(n, dtype=t.dtype, device=t.device).index_add_(0, h, sc) / deg_h.clamp(min=1)
+    mean_tail = torch.zeros(n, dtype=t.dtype, device=t.device).index_add_(0, tl, sc) / deg_t.clamp(min=1)
+    return score, logits, mean_head, mean_tail
+
+
+@torch.no_grad()
+def rel_rationale(graph, t, r, keep=None):
+    """(score [E], logits [E], mean_head [N], mean_tail [N]): KGRec's rationale scores, kgrec.py:165-188 (norm_attn_computer) with
+    t = entity_emb @ W_Q, and the two scatter_mean calls of :414-417.  Over the kept edges e = (h, tail, rel), with l_ea as in
+    rel_mh_attention:
+
+        logits_e = (l_e0 + l_e1) / 2,   score_e = softmax of logits over the kept edges of head entity h, times their number
+
+    both by edge id, 0 for an edge that is not kept; mean_head[n] / mean_tail[n] the mean of score over the kept edges whose head /
+    tail is n, 0 where there is none.  No gradient.  fp32 HIP tensors with d in {32, 64, 128} run csrc/rmha.hip (one walk by head for
+    the maxima, the sums and the scores, one by tail for the tail mean; no [E, d] tensor, no float atomics, equal bits twice);
+    everything else, and ops.KGREC_FUSED = False, the composed torch expression."""
+    _kgrec_args('rel_rationale', graph, t, r, keep)
+    t, r = t.detach(), r.detach()
+    if not _kgrec_kernel_path(graph, t, r):
+        if t.is_cuda:
+            with _DeterministicTorch():
+                return _rel_rationale_composed(graph, t, r, keep)
+        return _rel_rationale_composed(graph, t, r, keep)
+    if keep is not None:
+        keep = keep.to(t.device).to(torch.uint8).contiguous()
+    t, r = _mhcn_table(t), _mhcn_table(r)
+    N, d = t.shape
+    dev = t.device
+    E = graph.n_edges
+    lib = _lib.load()
+    kp = _ptr(keep) or None
+    score, logits = torch.zeros(max(E, 1), dtype=torch.float32, device=dev), torch.zeros(max(E, 1), dtype=torch.float32, device=dev)
+    mean_head, mean_tail = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
+    ls = graph.by_head
+    part_mz = torch.empty(max(ls.n_chunks, 1), 2, dtype=torch.float32, device=dev)
+    part_cnt = torch.empty(max(ls.n_chunks, 1), dtype=torch.int32, device=dev)
+    rc = lib.sslrec_rmha_score_f32(*ls.c_args(), t.data_ptr(), r.data_ptr(), r.shape[0], d, kp, logits.data_ptr(), score.data_ptr(),
+                                   mean_head.data_ptr(), part_mz.data_ptr(), part_cnt.data_ptr(), _stream())
+    _lib.check(rc, 'sslrec_rmha_score_f32')
+    ls = graph.by_tail
+    part_sum = torch.empty(max(ls.n_chunks, 1), dtype=torch.float32, device=dev)
+    part_cnt = torch.empty(max(ls.n_chunks, 1), dtype=torch.int32, device=dev)
+    rc = lib.sslrec_rmha_mean_f32(*ls.c_args(), kp, score.data_ptr(), mean_tail.data_ptr(), part_sum.data_ptr(), part_cnt.data_ptr(), _stream())
+    _lib.check(rc, 'sslrec_rmha_mean_f32')
+    return score[:E], logits[:E], mean_head, mean_tail
+
+
+# ----------------------------------------------------------------------------------------------
 # all-rank evaluation and negative sampling on the device (SURVEY.md §8f ranks 2 and 3)
 # ----------------------------------------------------------------------------------------------
 def full_predict(user_table, item_table, users, train_mask=None):
